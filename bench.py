@@ -31,11 +31,15 @@ all-reduce (shard) and the record gather after timing.
 
 Prints ONE JSON line on rank 0 (the driver's contract) with the roofline of
 the dominant kernel (hipEvents on the library's stream inside the timed
-steps), and after timing: the parity verdict of EVERY contig (the CPU oracle
+steps).  A plain run does no more: it sets up (genome, one count, one table
+build), warms up, times --steps steps, writes the last step's records with
+--dump-outputs DIR, and prints the line.  With --full, after timing: the
+parity verdict of EVERY contig (the CPU oracle
 on a thread pool, per rank on its own shard), at N=1 the CPU oracle timed on
 one pinned core over a bounded sample, the weighted-rank sub-line (BASELINE
 config 3, `configs.rank`, same genome and counts) with its own all-contig
-parity, the visit-histogram line and the host-pointer entry point.
+parity, the visit-histogram line and the host-pointer entry point; and the
+steady-state count and table timings (`setup_ms`, `end_to_end`).
 """
 from __future__ import annotations
 
@@ -73,6 +77,7 @@ LINE128_CEILING_GBS = 6170.0
 FETCH_B_PER_READ = {"k_pass1w": 128.0}   # physical bytes per FETCH_SIZE-tallied 64 B request: line bytes
 METRIC = "Gbases/sec scanned (k=13, log-ratio score) at 1/2/4/8 MI355X; spans bit-exact"
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "pmc_summary.json")
+DUMP_MAX_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files together (limit 64 MB, headers included)
 
 
 def cpu_model() -> str:
@@ -133,7 +138,34 @@ def parse(argv=None):
                         "one rank, so the multi-GPU code (count all-reduce, record gather + merge) runs on one GPU")
     p.add_argument("--multi-devices", default="0,0",
                    help="N=1: device list of the multi-device host-entry line (ks_set_devices; '' skips it)")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure: steady-state count and table timings (setup_ms, end_to_end), "
+                        "the CPU baseline, the parity verdicts against the CPU oracle, the weighted-rank sub-line, "
+                        "the visit-histogram line and the host-pointer entry points (each can be switched off with "
+                        "its --no-* option); without --full none of them runs")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step returned (the span records: "
+                        "pos 3 x n, score 2 x n) as DIR/<name>.npy in float64")
+    args = p.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = args.no_rank = args.no_visits = args.no_host_path = True
+        args.parity = "none"
+    return args
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step,
+    one float64 .npy each (the int32 positions are exact in float64), at
+    most DUMP_MAX_BYTES in all: of larger outputs a fixed, seeded sample of
+    the records (columns; the same ones of every array with as many)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(int(a.size) * 8 for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            n = int(a.shape[1])
+            keep = np.sort(np.random.default_rng(0).choice(n, size=int(n * (DUMP_MAX_BYTES / total)), replace=False))
+            a = a[:, keep]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ----------------------------------------------------------------- launcher
@@ -510,10 +542,11 @@ def main():
     with Timer() as tm:  # the first call also allocates the count's workspace
         words = D.count(ctx, ds, k, counts)
     setup["count_first_call_ms"] = round(tm.ms, 2)
-    counts.zero_()
-    with Timer() as tm:  # steady state (like table_device)
-        words = D.count(ctx, ds, k, counts)
-    setup["count_ms"] = round(tm.ms, 2)
+    if args.full:
+        counts.zero_()
+        with Timer() as tm:  # steady state (like table_device)
+            words = D.count(ctx, ds, k, counts)
+        setup["count_ms"] = round(tm.ms, 2)
     if args.mode == "shard" and dist:  # the table of the whole genome: exact int32 sum of per-shard counts
         from kmer_spans_amd.dist import allreduce_histogram
         with Timer() as tm:
@@ -541,7 +574,9 @@ def main():
                              "pieces": len(pieces_mine) if pieces_mine is not None else None,
                              "note": "one shard of an N-way LPT split (contigs cut inside N gaps) scanned with "
                                      "the whole genome's table"}
-    w_dev, thr, table, init_table, tt = make_table(counts, words, args.score)
+    w_dev, thr, table, init_table, tt = make_table(counts, words, args.score, warm=args.full)
+    if not args.full:  # the one build of a plain run is a first call (workspace growth, fresh VRAM)
+        tt["table_first_call"] = tt.pop("table_device")
     setup.update({key: round(v, 2) for key, v in tt.items()})
     table_shape = {"table_compressed": table.compressed, "table_distinct": table.distinct,
                    "line_kind": table.line_kind, "pass1_kernel": table.pass1_kernel,
@@ -550,6 +585,9 @@ def main():
 
     # ------------------------------------------------------------- timing
     pos, score, stats, elapsed = timed_steps(ds, table, init_table, args.steps, args.warmup)
+    if args.dump_outputs:  # this rank's records of the last timed step
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"pos" + sfx: pos, "score" + sfx: score})
 
     n_bases = int(stats[-1]["n_bases"])
     if args.mode == "shard":
@@ -662,9 +700,9 @@ def main():
                 extra["merged_regions"] = int(mpos.shape[1])
                 extra["merged_order_ok"] = bool(np.all(np.diff(mpos[0].astype(np.int64) * (1 << 32) + mpos[1]) > 0))
 
-    w = w_dev.cpu().numpy()
-    host = None
+    w = host = None
     if not args.no_cpu or not args.no_host_path:
+        w = w_dev.cpu().numpy()
         host = host_contigs(ds)
 
     # ---- PCIe-inclusive rate of the drop-in host entry point (never `value`)
@@ -780,7 +818,12 @@ def main():
         rank_line = rank_subline(args, ctx, ds, counts, words, make_table, timed_steps, host, D)
 
     step_ms = ms_step
-    e2e_ms = setup["count_ms"] + setup["table_device"] + step_ms
+    end_to_end = None  # from the steady-state count and table timings of --full
+    if args.full:
+        e2e_ms = setup["count_ms"] + setup["table_device"] + step_ms
+        end_to_end = {"ms": round(e2e_ms, 2), "Gbases_per_s": round(n_bases / (e2e_ms * 1e-3) / 1e9, 3),
+                      "what": "count + device score table from the counts (values, codes, 12-bit codes, "
+                              "expanded table) + one scan step, per rank"}
     line = {
         "metric": METRIC,
         "value": round(value, 4), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps,
@@ -806,9 +849,7 @@ def main():
         "host_path": host_path,
         "phase_ms": phase_means(stats),
         "setup_ms": setup,
-        "end_to_end": {"ms": round(e2e_ms, 2), "Gbases_per_s": round(n_bases / (e2e_ms * 1e-3) / 1e9, 3),
-                       "what": "count + device score table from the counts (values, codes, 12-bit codes, "
-                               "expanded table) + one scan step, per rank"},
+        "end_to_end": end_to_end,
         "configs": {"rank": rank_line} if rank_line is not None else None,
     }
     line.update(extra)
@@ -1126,6 +1167,9 @@ def run_genomes(args, ctx, ds0, dev, rank, world, dist, tdist, barrier, max_over
         elapsed = max_over_ranks(time.perf_counter() - t0)
     bases = sum(int(r[2]["n_bases"]) for r in results) * world
     n_regions = sum(int(r[0].shape[1]) for r in results)
+    if args.dump_outputs:  # a step is one genome end to end: this rank's last genome
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"pos" + sfx: results[-1][0], "score" + sfx: results[-1][1]})
     # parity of every genome of this rank after timing (each genome's own
     # table, rebuilt: the timed loop closed it), the oracle on a thread pool
     parity = None

@@ -97,13 +97,13 @@ def test_rccl_world1_allreduce_gather_merge(oracle, capsys):
 
 
 def test_bench_force_dist_runs_the_rccl_path(tmp_path):
-    """bench.py --gpus 1 --force-dist: the driver's multi-GPU command path
+    """bench.py --gpus 1 --full --force-dist: the driver's multi-GPU command path
     (process group over RCCL, count all-reduce, record gather + merge, parity
     reduced over ranks) at a small scale, as one rank: the line names the
     nccl backend, the merged records are in (seq_id, beg) order and equal the
     oracle's."""
     out = tmp_path / "b.json"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--scale", "0.02",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--scale", "0.02",
            "--steps", "2", "--warmup", "1", "--no-host-path", "--no-rank", "--no-visits", "--cpu-sample", "2e6",
            "--out", str(out)]
     env = dict(os.environ)

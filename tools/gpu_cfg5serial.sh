@@ -10,7 +10,7 @@ timeout -k 10 300 python tools/genome_phases.py --ext-gib 32 --reps 2 > $O/phase
 tail -3 $O/phases_32.txt
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --mode genomes --genomes-per-rank 3 --genomes-serial --no-cpu --out $O/g3.json > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --full --mode genomes --genomes-per-rank 3 --genomes-serial --no-cpu --out $O/g3.json > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
 F=$(find $O/prof -name '*kernel_trace.csv' | head -1)
 python3 $R/tools/timeline.py $F > $O/timeline.txt || true
 find $O/prof -name '*kernel_stats.csv' | head -1 | xargs -I{} sh -c 'cut -c1-150 {} | head -30'

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/${1:-cfg}
 P=${2:-ab}
 mkdir -p $OUT
 cd $R
-run() { tag=$1; shift; timeout -k 10 600 python bench.py --out $OUT/cfg_$tag.json "$@" > $OUT/cfg_$tag.log 2>&1 || { echo "FAILED $tag"; tail -20 $OUT/cfg_$tag.log; exit 1; }; python3 -c "import json;b=json.load(open('$OUT/cfg_$tag.json'));print('$tag', b['value'], b['ms_per_step'], b.get('parity_sample'), (b.get('roofline') or {}).get('frac'))"; }
+run() { tag=$1; shift; timeout -k 10 600 python bench.py --full --out $OUT/cfg_$tag.json "$@" > $OUT/cfg_$tag.log 2>&1 || { echo "FAILED $tag"; tail -20 $OUT/cfg_$tag.log; exit 1; }; python3 -c "import json;b=json.load(open('$OUT/cfg_$tag.json'));print('$tag', b['value'], b['ms_per_step'], b.get('parity_sample'), (b.get('roofline') or {}).get('frac'))"; }
 if [[ $P == *a* ]]; then
 run cfg2_chr1_k11 --ncontigs 1 --k 11 --steps 5 --warmup 1 --no-rank --no-host-path --no-visits
 run cfg3_pm1_k13 --score pm1 --k 13 --steps 5 --warmup 1 --no-rank --no-host-path --no-visits

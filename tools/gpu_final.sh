@@ -12,9 +12,9 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $O/pytest_gpu.txt
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1 || { tail -20 $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
-timeout -k 10 600 python bench.py --out $O/bench.json > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full --out $O/bench.json > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 python -c "import json;b=json.load(open('$O/bench.json'));print('bench', b['value'], b['ms_per_step'], b['roofline']['frac'], b['parity_sample'], b['parity_bp'], (b.get('host_path') or {}).get('Gbases_per_s'), (b.get('configs') or {}).get('rank', {}).get('value'))"
-B="--no-cpu --no-rank --no-host-path --no-visits"
+B="--full --no-cpu --no-rank --no-host-path --no-visits"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 $B --out $O/prof_bench.json > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }

@@ -6,7 +6,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1
-A="$2 --no-cpu --no-rank --no-host-path --no-visits --parity none"
+A="--full $2 --no-cpu --no-rank --no-host-path --no-visits --parity none"
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp

@@ -1,6 +1,6 @@
 """profiles/pmc_summary.json from the rocprofv3 --pmc passes of
-tools/gpu_pmc.sh (one counter group per run, `bench.py --steps 1 --warmup 0
---no-cpu`): per kernel the average FETCH_SIZE / WRITE_SIZE (KB) per dispatch
+tools/gpu_pmc.sh (one counter group per run, `bench.py --full --steps 1
+--warmup 0 --no-cpu`): per kernel the average FETCH_SIZE / WRITE_SIZE (KB) per dispatch
 and the dispatch count, tagged with the library build id and the workload
 bench.py compares before using them (bench.py pmc_traffic).
 
@@ -27,7 +27,7 @@ def main(bench_json, out_json, *csvs):
     p1 = cfg.get("pass1_kernel", "k_pass1p")
     out = {
         "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, tools/gpu_pmc.sh) of "
-                "`python bench.py --steps 1 --warmup 0 --no-cpu`; values in KB per dispatch (raw counters: "
+                "`python bench.py --full --steps 1 --warmup 0 --no-cpu`; values in KB per dispatch (raw counters: "
                 "FETCH_SIZE = TCC_EA0_RDREQ x 64 B, so 128-B streaming reads count half, MI355X_MICROARCH.md); "
                 "the scan's pass 1 is two dispatches per step (the two parts of the runs).",
         "build_id": cfg["build_id"],
