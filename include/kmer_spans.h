@@ -455,6 +455,72 @@ ks_status ks_windowed_dist(ks_ctx *ctx, const char *const *seqs, const int64_t *
 ks_status ks_windowed_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, const uint32_t *kmer_codes, int32_t kmer_n,
                           int32_t k, int32_t window, int32_t *dist_dev, int32_t *included_dev, int32_t *scores_dev);
 
+/* ---------------------------------------------------------------------
+ * Per-region q-mer spectra and Shannon entropy (csrc/ks_spectra.hip).
+ * --------------------------------------------------------------------- */
+
+/* What the reference's user script does with the regions next (test.R:703-720:
+ * subseq per region, oligonucleotideFrequency on both strands, -sum p log2 p),
+ * without taking the genome back to the host.
+ *
+ * Intervals: n triples (seq_id, beg, end); seq_id is a 0-based sequence index,
+ * beg..end are 1-based and inclusive in that sequence's coordinates -- the
+ * numbers ks_scan_dev / ks_kmer_regions return, read as test.R:706 reads them
+ * (subseq(seq[id + 1], beg, end)); ks_tr_lr_* regions carry seq_id + 1, so
+ * subtract 1 from those.  An interval covers bytes seq[beg-1 .. end-1]; it is
+ * valid when 0 <= seq_id < nseq, beg >= 1, end <= length and end >= beg - 1
+ * (width 0 is valid).  Intervals may overlap, repeat and come in any order;
+ * row i of the outputs belongs to interval i.
+ * Words: every window of q consecutive bytes wholly inside the interval that
+ * holds no N/n counts once; no end-of-run quirks apply (Q1 and Q5 belong to
+ * the scan).  Bytes are coded (c >> 1) & 3 as everywhere here.  Biostrings'
+ * oligonucleotideFrequency skips windows holding any non-ACGT letter; this
+ * skips only N/n and codes every other byte as it falls.
+ * Columns: spectra is n x 4^q uint32, row-major; bin c is the word with code
+ * c, first base most significant, in the order of ks_kmer_seq(q) (internal
+ * A,C,T,G, not Biostrings' alphabetical order).  1 <= q <= KS_SPECTRA_MAX_Q.
+ * flags & KS_SPECTRA_BOTH_STRANDS: row[c] = n[c] + n[rc(c)], rc(c) = the q
+ * two-bit digits reversed and each XORed with 2 (proportional to fwd + rev of
+ * test.R:707-709); otherwise row[c] = n[c].  A sequence has < 2^31 bytes, so
+ * no bin wraps: the counts are exact.
+ * Entropy: T = sum(row), H = -sum over row[c] > 0 of (row[c] / T) log2(row[c]
+ * / T) in FP64 (device log2; within 4^q * 2q * 2^-52 of the exactly summed
+ * value); NaN when T = 0 (width < q or all N), as R's 0/0 gives.
+ * n = 0 is KS_OK and touches nothing.  ctx == NULL is the default context on
+ * device 0; the call is never spread over a device list (ks_set_devices) and
+ * is not forwarded by the fork broker: it takes the usual context-entry
+ * checks only. */
+#define KS_SPECTRA_MAX_Q 6
+#define KS_SPECTRA_BOTH_STRANDS 1
+typedef struct ks_spectra_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total, ms_plan, ms_count, ms_entropy;
+  int64_t n_regions;
+  int64_t n_bases; /* sum of widths */
+  int64_t n_words; /* sum of single-strand counts */
+  int64_t n_tiles; /* work tiles of the counting kernel */
+} ks_spectra_stats;
+
+/* Device-resident: the three interval arrays, spectra_dev (n x 4^q uint32,
+ * row-major, OVERWRITTEN -- the caller need not zero it) and entropy_dev (n
+ * doubles, may be NULL: the entropy pass is skipped) are device pointers.
+ * The intervals are checked on the device before any kernel reads a
+ * sequence through them: a bad one returns KS_ERR_ARG ("interval i out of
+ * range", the first such i) with no kernel launched on the sequences and the
+ * outputs untouched.  stats may be NULL. */
+ks_status ks_region_spectra_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, const int32_t *seq_id_dev,
+                                const int32_t *beg_dev, const int32_t *end_dev, int64_t n, int32_t q,
+                                int32_t flags, uint32_t *spectra_dev, double *entropy_dev,
+                                ks_spectra_stats *stats);
+/* Host buffers: validates everything, intervals included, before any device
+ * call; stages the sequences like ks_kmer_counts does, uploads the intervals,
+ * runs the device entry, copies spectra (n x 4^q) and entropy (n, may be
+ * NULL) back. */
+ks_status ks_region_spectra(ks_ctx *ctx, const char *const *seqs, const int64_t *lens, int32_t nseq,
+                            const int32_t *seq_id, const int32_t *beg, const int32_t *end, int64_t n,
+                            int32_t q, int32_t flags, uint32_t *spectra, double *entropy);
+/* Bases per work tile of the counting kernel (tests place seams with it). */
+int32_t ks_spectra_tile_bases(void);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

@@ -58,6 +58,15 @@ class TableInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class SpectraStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_plan", C.c_double), ("ms_count", C.c_double),
+                ("ms_entropy", C.c_double), ("n_regions", C.c_int64), ("n_bases", C.c_int64),
+                ("n_words", C.c_int64), ("n_tiles", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -89,7 +98,11 @@ EXPORTS = [
     "ks_release_cache", "ks_set_fork_broker", "ks_set_host_cache",
     "ks_set_devices", "ks_get_devices", "ks_shard_plan", "ks_merge_parts", "ks_set_host_cache_idle",
     "ks_multi_last_stats",
+    "ks_region_spectra", "ks_region_spectra_dev", "ks_spectra_tile_bases",
 ]
+
+KS_SPECTRA_MAX_Q = 6
+KS_SPECTRA_BOTH_STRANDS = 1
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -155,6 +168,9 @@ def load():
         "ks_shard_plan": ([P, P, I32, I32, P, I64], I64),
         "ks_merge_parts": ([P, I64, I32, P, P], I32),
         "ks_multi_last_stats": ([P, I32], I32),
+        "ks_region_spectra": ([P, P, P, I32, P, P, P, I64, I32, I32, P, P], I32),
+        "ks_region_spectra_dev": ([P, P, P, P, P, I64, I32, I32, P, P, P], I32),
+        "ks_spectra_tile_bases": ([], I32),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

@@ -12,6 +12,8 @@ layout and error behaviour as /root/reference/kmer_spans.R:
   read_kmers(fname, magic)                        :162-186
   read_fasta(path, min_len=0)   (readDNAStringSet + as.character, :136-144)
   window_kmer_dist(seq, kmers, window, freq=True, ret_flag=0)  :103-118
+  region_spectra(seq, pos, q=4, both_strands=True)   (test.R:703-720: subseq +
+                 oligonucleotideFrequency on both strands + Shannon entropy)
 
 Sequences are a str/bytes or a list of them (R character vectors).  Results
 come from libkmerspans.so on the GPU; nothing here computes a result on the
@@ -182,6 +184,52 @@ def lr_regions(seq, params, kmers, kmer_scores, trans_scores, device: int = 0) -
     pos, score = regions_to_numpy(r)
     reg = {"seq_i": pos[0], "beg": pos[1], "end": pos[2], "score": score[0], "null": score[1]}
     return {"kmer_scores": spectra.reshape(2, nk).T.copy(), "reg": reg, "pos": pos, "score": score}
+
+
+def _pos_rows(pos):
+    """(seq_id, beg, end) int32 rows of a region matrix given as [3, R]
+    (kmer_regions) or [R, 3] (kmer_low_comp_regions).  A 3 x 3 input is read
+    as [3, R]."""
+    a = np.asarray(pos)
+    if a.ndim != 2 or 3 not in a.shape:
+        raise KmerSpansError("pos must be a [3, R] or [R, 3] matrix of (seq_id, beg, end)")
+    if a.shape[0] != 3:
+        a = a.T
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return a[0], a[1], a[2]
+
+
+def region_spectra(seq, pos, q: int = 4, both_strands: bool = True, seq_base: int = 0, device: int = 0) -> dict:
+    """The q-mer spectrum and Shannon entropy of every region (what test.R:
+    703-720 computes with subseq + oligonucleotideFrequency, on the GPU).
+
+    pos: the regions as kmer_regions returns them ([3, R]: seq_id, beg, end)
+    or as kmer_low_comp_regions does ([R, 3]); both are accepted by shape, a
+    3 x 3 matrix is read as [3, R].  seq_id is 0-based (seq_base=1 for the
+    1-based ids of lr_regions), beg..end 1-based inclusive.  Returns
+    {'kmers': kmer_seq(q), 'counts': uint32[R, 4^q] (columns in kmer_seq(q)
+    order -- internal A,C,T,G, not alphabetical; both strands folded,
+    n[c] + n[rc(c)], when both_strands), 'freq': float64[R, 4^q] = counts /
+    row sum (NaN rows where the sum is 0), 'entropy': float64[R] (NaN there
+    too)}.  Windows holding N/n are skipped; unlike Biostrings, other non-ACGT
+    letters are coded (c >> 1) & 3 like everywhere in this library."""
+    q = int(q)
+    sid, beg, end = _pos_rows(pos)
+    if seq_base:
+        sid = sid - np.int32(seq_base)
+    n = int(sid.size)
+    hs = _HostSeqs(seq)
+    nb = 4 ** q if 1 <= q <= _lib.KS_SPECTRA_MAX_Q else 1
+    counts = np.zeros((n, nb), dtype=np.uint32)
+    ent = np.zeros(n, dtype=np.float64)
+    sid, beg, end = (np.ascontiguousarray(x, dtype=np.int32) for x in (sid, beg, end))
+    check(load().ks_region_spectra(_ctx(device), hs.ptrs, hs.lens.ctypes.data, hs.n, sid.ctypes.data,
+                                   beg.ctypes.data, end.ctypes.data, n, q,
+                                   _lib.KS_SPECTRA_BOTH_STRANDS if both_strands else 0,
+                                   counts.ctypes.data, ent.ctypes.data))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        freq = counts / counts.sum(axis=1, dtype=np.float64)[:, None]
+    return {"kmers": kmer_seq(q), "counts": counts, "freq": freq, "entropy": ent}
 
 
 # ------------------------------------------------------------ table builders

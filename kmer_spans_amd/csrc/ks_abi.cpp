@@ -263,13 +263,6 @@ ks_status ensure_pinned(ks_ctx *ctx, size_t bytes, void **out) {
   return KS_OK;
 }
 
-namespace {
-
-struct HostEnd {  // host_call_end when a host-buffer entry point returns
-  ks_ctx *c;
-  ~HostEnd() { host_call_end(c); }
-};
-
 ks_status check_seqs(const char *const *seqs, const int64_t *lens, int32_t nseq) {
   if (nseq < 1 || !seqs || !lens)
     return fail(KS_ERR_ARG, "seq_r must be a character vector of length at least one");
@@ -289,6 +282,8 @@ ks_status check_dev_seqs(const ks_dev_seqs *s) {
     if (s->offsets_host[q + 1] < s->offsets_host[q]) return fail(KS_ERR_ARG, "offsets must be non-decreasing");
   return KS_OK;
 }
+
+namespace {
 
 std::mutex g_default_mu;
 ks_ctx *g_default = nullptr;

@@ -227,6 +227,9 @@ ks_status copy_out(ks_ctx *ctx, void *dst, const void *src_dev, size_t n);
 // (synchronises ctx->stream)
 ks_status h2d_pinned(ks_ctx *ctx, void *dst_dev, const void *src, size_t n, int nthr);
 ks_status activate(ks_ctx *ctx);  // fork check + hipSetDevice
+// Argument checks shared by the entry points (ks_abi.cpp).
+ks_status check_seqs(const char *const *seqs, const int64_t *lens, int32_t nseq);
+ks_status check_dev_seqs(const ks_dev_seqs *s);
 // A context is used by one thread at a time (include/kmer_spans.h): an entry
 // point marks its context as in use for its duration (nested entry points
 // of the same thread pass), and a call from a second thread meanwhile fails
@@ -272,6 +275,10 @@ void pool_release_device(int dev);             // free the device's pooled expan
 // device memory (ctx's and its sub-context's workspace, the pooled table
 // buffer) goes back to the driver.
 void host_call_end(ks_ctx *ctx);
+struct HostEnd {  // host_call_end when a host-buffer entry point returns
+  ks_ctx *c;
+  ~HostEnd() { host_call_end(c); }
+};
 void janitor_forget(ks_ctx *ctx);  // (ks_ctx_destroy) off the timed-release list
 void janitor_release_all();        // (ks_release_cache) the listed contexts' memory back now
 ks_status default_ctx(ks_ctx **ctx);  // *ctx or the process default context (fork-checked)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DevSeqs, Fasta, Regions, ScanStats, check, load, regions_to_numpy
+from ._lib import DevSeqs, Fasta, Regions, ScanStats, SpectraStats, check, load, regions_to_numpy
 
 
 @dataclass
@@ -336,3 +336,55 @@ def windowed(ctx: _lib.Context, ds, kmer_codes, k: int, window: int, dist: torch
                                  C.c_void_p(dist.data_ptr()),
                                  C.c_void_p(included.data_ptr()) if included is not None else None,
                                  C.c_void_p(scores.data_ptr()) if scores is not None else None))
+
+
+def region_spectra(ctx: _lib.Context, ds, pos, q: int = 4, both_strands: bool = True, entropy: bool = True,
+                   seq_base: int = 0, out: torch.Tensor | None = None):
+    """ks_region_spectra_dev: the q-mer spectrum and Shannon entropy of every
+    region of device-resident sequences (ds: DeviceSeqs or FastaSeqs).
+
+    pos: the int32[3, R] array scan() / tr_lr() return (rows seq_id, beg, end;
+    beg..end 1-based inclusive), as numpy (uploaded) or as an int32 CUDA tensor
+    (used in place).  seq_base=1 subtracts 1 from the sequence ids (tr_lr
+    regions carry 1-based ids).  Returns (counts, entropy, stats):
+    counts  int32 CUDA tensor [R, 4**q] holding the library's uint32 bits
+            (torch has no uint32 arithmetic; a bin above 2^31 - 1 reads
+            negative -- view the host copy as np.uint32), columns in
+            kmer_seq(q) order, both strands folded when both_strands;
+            out= (int32 CUDA, contiguous, R * 4**q elements) is reused for it;
+            every row is overwritten;
+    entropy float64 CUDA tensor [R] (NaN where a row is empty), or None;
+    stats   dict of ks_spectra_stats."""
+    q = int(q)
+    dev = ds.seq.device if hasattr(ds, "seq") else torch.device("cuda", getattr(ctx, "device", 0))
+    if isinstance(pos, torch.Tensor):
+        if pos.dtype != torch.int32 or not pos.is_cuda or pos.dim() != 2 or pos.shape[0] != 3:
+            raise _lib.KmerSpansError("pos must be an int32 [3, R] array (numpy or cuda tensor)")
+        if hasattr(ds, "seq") and pos.device != ds.seq.device:
+            raise _lib.KmerSpansError(f"pos is on {pos.device}, the sequences are on {ds.seq.device}")
+        p = pos.contiguous()
+    else:
+        a = np.asarray(pos)
+        if a.ndim != 2 or a.shape[0] != 3:
+            raise _lib.KmerSpansError("pos must be an int32 [3, R] array (numpy or cuda tensor)")
+        p = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    n = int(p.shape[1])
+    ids = p[0] - int(seq_base) if seq_base else p[0]
+    nb = 4 ** q if 1 <= q <= _lib.KS_SPECTRA_MAX_Q else 1
+    if out is not None:
+        if out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.numel() != n * nb:
+            raise _lib.KmerSpansError("out must be a contiguous int32 cuda tensor of R * 4^q elements")
+        counts = out.view(n, nb)
+    else:
+        counts = torch.empty((n, nb), dtype=torch.int32, device=p.device)
+    ent = torch.empty(n, dtype=torch.float64, device=p.device) if entropy else None
+    st = SpectraStats()
+    s = ds.struct()
+    _order(ctx)
+    check(load().ks_region_spectra_dev(ctx.handle if ctx is not None else None, C.byref(s),
+                                       C.c_void_p(ids.data_ptr()), C.c_void_p(p[1].data_ptr()),
+                                       C.c_void_p(p[2].data_ptr()), n, q,
+                                       _lib.KS_SPECTRA_BOTH_STRANDS if both_strands else 0,
+                                       C.c_void_p(counts.data_ptr()),
+                                       C.c_void_p(ent.data_ptr()) if ent is not None else None, C.byref(st)))
+    return counts, ent, st.as_dict()
