@@ -521,6 +521,84 @@ ks_status ks_region_spectra(ks_ctx *ctx, const char *const *seqs, const int64_t 
 /* Bases per work tile of the counting kernel (tests place seams with it). */
 int32_t ks_spectra_tile_bases(void);
 
+/* ---------------------------------------------------------------------
+ * Pairwise distances between region spectra (csrc/ks_spectra_dist.hip).
+ * --------------------------------------------------------------------- */
+
+/* What the reference's author does with the spectra next (test.R:762-807):
+ * dist() of the strand-folded, row-normalised tetramer spectra -- the
+ * Euclidean distance between every pair of rows -- for all regions and for a
+ * row subset, without taking the counts back to the host.
+ *
+ * Input: a spectra matrix as ks_region_spectra_dev writes it, n x ncol uint32,
+ * row-major.  1 <= ncol <= KS_DIST_MAX_NCOL (4^6); ncol is not tied to a q.
+ * Profile of a row: p[k] = (double)c[k] / (double)T, T the row sum accumulated
+ * in 64-bit integers (below 2^44, so its conversion is exact); one IEEE
+ * division per element.  For a both-strands row this is the (fwd + rev) / 2
+ * of test.R:707-709.
+ * Distance of rows i and j, fixed as an order of operations: acc = 0; for
+ * k = 0 .. ncol - 1 ascending: d = p_i[k] - p_j[k]; acc = acc + d * d, with the
+ * subtraction, the multiplication and the addition separate FP64 operations
+ * (no FMA) and one accumulator per pair.  flags & KS_DIST_SQUARED returns acc,
+ * otherwise the result is sqrt(acc).  A row with T = 0 gives NaN against every
+ * row (the natural 0 / 0).  It follows that the bits can be predicted on the
+ * host, that d(i, j) and d(j, i) are the same bits, that a row against itself
+ * is exactly 0, and that rows whose counts are proportional (c_j = f * c_i)
+ * are at exactly 0: the correctly rounded division gives both the same p.
+ *
+ * Row selections: an optional array of int64 row indices into the matrix, in
+ * any order, repeats allowed.  NULL with a count of m means rows 0 .. m - 1 in
+ * order (pass m = n for all rows; m > n is an error then).
+ * Condensed form: all pairs i < j of the m selected rows; out holds
+ * m (m - 1) / 2 doubles in the order of R's dist object (scipy's pdist): pair
+ * (i < j) at i * m - i (i + 1) / 2 + (j - i - 1).  m = 0 or 1 is valid and
+ * writes nothing.
+ * Cross form: selected rows A (na) against selected rows B (nb), a dense
+ * na x nb row-major block -- the way to walk a list too large for one matrix
+ * block by block, or to measure regions against a few centroids.  na = 0 or
+ * nb = 0 writes nothing.
+ * All output offsets are 64-bit (the condensed form passes 2^31 entries at
+ * m = 65,537).  The caller owns the output.  ctx == NULL is the default
+ * context on device 0; the calls are never spread over a device list and are
+ * not forwarded by the fork broker. */
+#define KS_DIST_MAX_NCOL 4096
+#define KS_DIST_SQUARED 1
+typedef struct ks_dist_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total, ms_normalise, ms_distance;
+  int64_t n_pairs;       /* distances computed and written */
+  int64_t bytes_written; /* 8 * n_pairs */
+  int64_t panel_bytes;   /* the FP64 profile panel the call allocated and freed */
+} ks_dist_stats;
+
+/* Device-resident: spectra_dev, the selections and out_dev are device
+ * pointers.  The indices are checked on the device before anything is
+ * written: a bad one returns KS_ERR_ARG ("row index s out of range", s the
+ * first such position in its selection) with the output untouched.  The only
+ * allocation is the FP64 profile panel of the selected rows ((m or na + nb) x
+ * ncol x 8 bytes; KS_ERR_NOMEM if it fails), freed before return.  stats may
+ * be NULL. */
+ks_status ks_spectra_dist_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                              const int64_t *rows_dev, int64_t m, int32_t flags, double *out_dev,
+                              ks_dist_stats *stats);
+ks_status ks_spectra_cross_dist_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                                    const int64_t *rows_a_dev, int64_t na, const int64_t *rows_b_dev,
+                                    int64_t nb, int32_t flags, double *out_dev, ks_dist_stats *stats);
+/* Host buffers: validates every argument and every index before any device
+ * call, then uploads, runs the device entry and copies the result back. */
+ks_status ks_spectra_dist(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                          int64_t m, int32_t flags, double *out);
+ks_status ks_spectra_cross_dist(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol,
+                                const int64_t *rows_a, int64_t na, const int64_t *rows_b, int64_t nb,
+                                int32_t flags, double *out);
+/* The kernels' index arithmetic on the host (csrc/ks_dist_index.h; tests walk
+ * it where a GPU run would need terabytes of output): off[x] = the condensed
+ * offset of pair (i[x] < j[x]) of m rows; (row[x], col[x]) = the tile that
+ * linear id t[x] names among the tiles on or above the diagonal of a
+ * tiles x tiles grid; the rows (= columns) of pairs per tile. */
+void ks_dist_pair_offsets(const int64_t *i, const int64_t *j, int64_t cnt, int64_t m, int64_t *off);
+void ks_dist_tiles_of(const int64_t *t, int64_t cnt, int64_t tiles, int64_t *row, int64_t *col);
+int32_t ks_dist_tile_rows(void);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

@@ -67,6 +67,14 @@ class SpectraStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class DistStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_distance", C.c_double),
+                ("n_pairs", C.c_int64), ("bytes_written", C.c_int64), ("panel_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -99,10 +107,14 @@ EXPORTS = [
     "ks_set_devices", "ks_get_devices", "ks_shard_plan", "ks_merge_parts", "ks_set_host_cache_idle",
     "ks_multi_last_stats",
     "ks_region_spectra", "ks_region_spectra_dev", "ks_spectra_tile_bases",
+    "ks_spectra_dist", "ks_spectra_dist_dev", "ks_spectra_cross_dist", "ks_spectra_cross_dist_dev",
+    "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
 ]
 
 KS_SPECTRA_MAX_Q = 6
 KS_SPECTRA_BOTH_STRANDS = 1
+KS_DIST_MAX_NCOL = 4096
+KS_DIST_SQUARED = 1
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -171,6 +183,13 @@ def load():
         "ks_region_spectra": ([P, P, P, I32, P, P, P, I64, I32, I32, P, P], I32),
         "ks_region_spectra_dev": ([P, P, P, P, P, I64, I32, I32, P, P, P], I32),
         "ks_spectra_tile_bases": ([], I32),
+        "ks_spectra_dist": ([P, P, I64, I32, P, I64, I32, P], I32),
+        "ks_spectra_dist_dev": ([P, P, I64, I32, P, I64, I32, P, P], I32),
+        "ks_spectra_cross_dist": ([P, P, I64, I32, P, I64, P, I64, I32, P], I32),
+        "ks_spectra_cross_dist_dev": ([P, P, I64, I32, P, I64, P, I64, I32, P, P], I32),
+        "ks_dist_pair_offsets": ([P, P, I64, I64, P], None),
+        "ks_dist_tiles_of": ([P, I64, I64, P, P], None),
+        "ks_dist_tile_rows": ([], I32),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

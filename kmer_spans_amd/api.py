@@ -14,6 +14,8 @@ layout and error behaviour as /root/reference/kmer_spans.R:
   window_kmer_dist(seq, kmers, window, freq=True, ret_flag=0)  :103-118
   region_spectra(seq, pos, q=4, both_strands=True)   (test.R:703-720: subseq +
                  oligonucleotideFrequency on both strands + Shannon entropy)
+  region_distances(counts, rows=None, rows_b=None, squared=False)   (test.R:
+                 762-807: dist() of the row-normalised spectra)
 
 Sequences are a str/bytes or a list of them (R character vectors).  Results
 come from libkmerspans.so on the GPU; nothing here computes a result on the
@@ -230,6 +232,54 @@ def region_spectra(seq, pos, q: int = 4, both_strands: bool = True, seq_base: in
     with np.errstate(invalid="ignore", divide="ignore"):
         freq = counts / counts.sum(axis=1, dtype=np.float64)[:, None]
     return {"kmers": kmer_seq(q), "counts": counts, "freq": freq, "entropy": ent}
+
+
+def _rows_arg(rows, what):
+    if rows is None:
+        return None
+    r = np.asarray(rows)
+    if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
+        raise KmerSpansError(f"{what} must be a 1-d array of integer row indices")
+    return np.ascontiguousarray(r, dtype=np.int64)
+
+
+def region_distances(counts, rows=None, rows_b=None, squared: bool = False, device: int = 0) -> np.ndarray:
+    """Euclidean distances between row-normalised spectra (R's dist() on
+    reg.kmer.sp, test.R:762-807) from the counts region_spectra returns.
+
+    counts: [n, ncol] non-negative integers (uint32 range), 1 <= ncol <= 4096.
+    A row's profile is counts / row sum; the distance of two rows is the FP64
+    sum over the columns, in order, of the squared profile differences --
+    squared=True returns that sum, otherwise its square root.  An empty row
+    is NaN against every row; rows with proportional counts are at exactly 0.
+    rows / rows_b: optional integer row indices (any order, repeats allowed).
+    rows_b is None: the condensed form, float64[m(m-1)/2] over the pairs i < j
+    of the selected rows (all rows when rows is None) in the order of R's dist
+    object and scipy's pdist.  Otherwise the dense float64[na, nb] block of
+    rows (all rows when None) against rows_b."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "iu":
+        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
+    if c.dtype != np.uint32:
+        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+            raise KmerSpansError("counts must be in the uint32 range")
+        c = c.astype(np.uint32)
+    c = np.ascontiguousarray(c)
+    n, ncol = (int(x) for x in c.shape)
+    ra, rb = _rows_arg(rows, "rows"), _rows_arg(rows_b, "rows_b")
+    na = n if ra is None else int(ra.size)
+    flags = _lib.KS_DIST_SQUARED if squared else 0
+    L = load()
+    if rows_b is None:
+        out = np.zeros(na * (na - 1) // 2 if na > 1 else 0, dtype=np.float64)
+        check(L.ks_spectra_dist(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None,
+                                na, flags, out.ctypes.data))
+        return out
+    nb = int(rb.size)
+    out = np.zeros((na, nb), dtype=np.float64)
+    check(L.ks_spectra_cross_dist(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None,
+                                  na, rb.ctypes.data, nb, flags, out.ctypes.data))
+    return out
 
 
 # ------------------------------------------------------------ table builders

@@ -79,7 +79,8 @@ constexpr int kScLayout = 8;       // run_layout: 8 aggregates [8, 16)
 constexpr int kScRegions = 16;     // scan_core: region counters [16, 16 + kSegs)
 constexpr int kScSumWords = 96;    // count_words: sum of a histogram
 constexpr int kScMultiWords = 104; // launch_count_multi: words per k of a batch [104, 112)
-constexpr int kScEnd = 112;
+constexpr int kScDistBad = 112;    // dist_impl: first bad row index of each selection [112, 114)
+constexpr int kScEnd = 114;
 
 struct DevBuf {
   void *ptr = nullptr;

@@ -388,3 +388,66 @@ def region_spectra(ctx: _lib.Context, ds, pos, q: int = 4, both_strands: bool = 
                                        C.c_void_p(counts.data_ptr()),
                                        C.c_void_p(ent.data_ptr()) if ent is not None else None, C.byref(st)))
     return counts, ent, st.as_dict()
+
+
+def _rows_dev(rows, what, dev):
+    """A row selection as a contiguous int64 CUDA tensor (numpy is uploaded)."""
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.int64 or not rows.is_cuda or rows.dim() != 1:
+            raise _lib.KmerSpansError(f"{what} must be a 1-d int64 array (numpy or cuda tensor)")
+        if rows.device != dev:
+            raise _lib.KmerSpansError(f"{what} is on {rows.device}, the counts are on {dev}")
+        return rows.contiguous()
+    a = np.asarray(rows)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise _lib.KmerSpansError(f"{what} must be a 1-d int64 array (numpy or cuda tensor)")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+
+def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=None, squared: bool = False,
+                     out: torch.Tensor | None = None):
+    """ks_spectra_dist_dev / ks_spectra_cross_dist_dev: Euclidean distances
+    between the row-normalised spectra of region_spectra, on the device.
+
+    counts: the int32 CUDA tensor [n, ncol] region_spectra returns (uint32
+    bits), used in place.  rows / rows_b: optional selections of row indices,
+    int64 CUDA tensors (used in place) or numpy (uploaded); any order, repeats
+    allowed; None = all rows.  rows_b is None: the condensed form, a float64
+    CUDA tensor [m(m-1)/2] over the pairs i < j of the selected rows in the
+    order of R's dist object (scipy's pdist).  Otherwise the dense [na, nb]
+    block of rows against rows_b.  squared=True skips the square root.  out=
+    (float64 CUDA, contiguous, as many elements) is reused for the result.
+    Returns (distances, stats dict of ks_dist_stats)."""
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
+            or counts.dim() != 2 or not counts.is_contiguous()):
+        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
+    dev = counts.device
+    n, ncol = int(counts.shape[0]), int(counts.shape[1])
+    ra = _rows_dev(rows, "rows", dev) if rows is not None else None
+    rb = _rows_dev(rows_b, "rows_b", dev) if rows_b is not None else None
+    na = n if ra is None else int(ra.numel())
+    if rb is None:
+        shape = (na * (na - 1) // 2 if na > 1 else 0,)
+    else:
+        shape = (na, int(rb.numel()))
+    numel = int(np.prod(shape, dtype=np.int64))
+    if out is not None:
+        if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.numel() != numel:
+            raise _lib.KmerSpansError(f"out must be a contiguous float64 cuda tensor of {numel} elements")
+        if out.device != dev:
+            raise _lib.KmerSpansError(f"out is on {out.device}, the counts are on {dev}")
+        res = out.view(shape)
+    else:
+        res = torch.empty(shape, dtype=torch.float64, device=dev)
+    st = _lib.DistStats()
+    flags = _lib.KS_DIST_SQUARED if squared else 0
+    h = ctx.handle if ctx is not None else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    _order(ctx)
+    if rb is None:
+        check(load().ks_spectra_dist_dev(h, C.c_void_p(counts.data_ptr()), n, ncol, ptr(ra), na, flags, ptr(res),
+                                         C.byref(st)))
+    else:
+        check(load().ks_spectra_cross_dist_dev(h, C.c_void_p(counts.data_ptr()), n, ncol, ptr(ra), na, ptr(rb),
+                                               int(rb.numel()), flags, ptr(res), C.byref(st)))
+    return res, st.as_dict()
