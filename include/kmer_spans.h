@@ -599,6 +599,97 @@ void ks_dist_pair_offsets(const int64_t *i, const int64_t *j, int64_t cnt, int64
 void ks_dist_tiles_of(const int64_t *t, int64_t cnt, int64_t tiles, int64_t *row, int64_t *col);
 int32_t ks_dist_tile_rows(void);
 
+/* ---------------------------------------------------------------------
+ * Hierarchical clustering of a condensed dissimilarity vector
+ * (csrc/ks_hclust.hip).
+ * --------------------------------------------------------------------- */
+
+/* The line after dist() in the reference author's analysis (test.R:776,
+ * :805): hclust() of the distances, then a cut of the tree into groups of
+ * bounded diameter (test.R:826-859) -- without taking the matrix to the host.
+ *
+ * Input: a condensed dissimilarity vector as ks_spectra_dist_dev writes it,
+ * n (n - 1) / 2 doubles, pair i < j at i * n - i (i + 1) / 2 + (j - i - 1)
+ * (64-bit offsets).  n >= 2.  Every entry must be finite: a NaN (an empty
+ * spectrum row gives one) or an infinity is KS_ERR_ARG, "dissimilarity at
+ * offset o is not finite", o the first such offset.  The device entry checks
+ * that on the device before anything is modified; after a rejected call the
+ * input is untouched and the context usable.
+ *
+ * Algorithm: the nearest-neighbour-list agglomeration of R's hclust
+ * (F. Murtagh's), fixed here in 0-based terms so that a short host loop
+ * reproduces it exactly.  State: live[i] (all true), size[i] (all 1.0), the
+ * matrix D(i, j), and for i = 0 .. n - 2 the pair nn[i], dnn[i]: nn[i] is the
+ * j > i with live[j] that has the smallest D(i, j), scanning j ascending with
+ * a strict <, so the lowest j wins a tie; dnn[i] is that value, +inf if no
+ * such j exists.  Step s = 0 .. n - 2:
+ *   1. im = the live i in 0 .. n - 2 with the smallest dnn[i] (ascending,
+ *      strict <: the lowest i wins);
+ *   2. jm = nn[im], a = min(im, jm), b = max(im, jm);
+ *   3. ia[s] = a, ib[s] = b, height[s] = dnn[im]; live[b] = false;
+ *   4. for every live k != a:
+ *        complete: D(a, k) = D(b, k) if D(b, k) > D(a, k), else unchanged;
+ *        single:   D(a, k) = D(b, k) if D(b, k) < D(a, k), else unchanged;
+ *        average:  D(a, k) = (size[a] * D(a, k) + size[b] * D(b, k))
+ *                            / (size[a] + size[b]),
+ *                  two multiplications, an addition and a division as separate
+ *                  FP64 operations (no FMA);
+ *   5. size[a] += size[b];
+ *   6. nn / dnn are recomputed by the scan above for row a and for every live
+ *      i whose nn[i] was a or b, and for no other row.
+ * -0.0 and +0.0 compare equal, so the index decides between them.  For
+ * complete and single linkage every height has the bits of an input entry.
+ * If average linkage overflows until no finite minimum is left the call fails
+ * with KS_ERR_ARG.
+ *
+ * Outputs (host pointers, 16 n bytes in all), as in R's hclust object:
+ *   merge  [n - 1][2] int32, row-major.  Observation i (0-based) appears as
+ *          -(i + 1), the cluster made at step t (0-based) as t + 1.  Within a
+ *          row a singleton comes before a cluster; of two singletons the
+ *          smaller observation comes first, of two clusters the earlier step.
+ *   height n - 1 doubles in step order.
+ *   order  n int32, 1-based: the leaves of the final tree from left to right,
+ *          merge[s][0] on the left (R's $order).
+ * The step loop, ia / ib and height are device work; the O(n) conversion to
+ * merge and order is host code. */
+#define KS_HCLUST_COMPLETE 0
+#define KS_HCLUST_SINGLE 1
+#define KS_HCLUST_AVERAGE 2
+#define KS_HCLUST_KEEP_INPUT 1 /* flags: cluster a device copy, leave diss_dev untouched */
+typedef struct ks_hclust_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total; /* first check launch to the end of the merge kernel */
+  double ms_check; /* the finiteness pass */
+  double ms_init;  /* the KEEP_INPUT copy, if any, and the initial nearest-neighbour list */
+  double ms_merge; /* the n - 1 steps */
+  int64_t n;
+  int64_t n_rescans;  /* rows whose nearest neighbour was recomputed after the start (row a of every step included) */
+  int64_t work_bytes; /* device memory the call allocated and freed: the KEEP_INPUT copy */
+} ks_hclust_stats;
+
+/* diss_dev is a device pointer.  Without KS_HCLUST_KEEP_INPUT it is
+ * OVERWRITTEN (the matrix is updated in place); with the flag the call
+ * allocates a copy (KS_ERR_NOMEM if it cannot) and the input's bits are
+ * unchanged afterwards.  The O(n) state (41 n bytes) comes from the context
+ * workspace and is not counted in work_bytes.  All arguments are validated
+ * before any device call (n < 2, an unknown method, unknown flag bits, null
+ * pointers).  stats may be NULL.  ctx == NULL is the default context on device
+ * 0; the calls are never spread over a device list and are not forwarded by
+ * the fork broker. */
+ks_status ks_hclust_dev(ks_ctx *ctx, double *diss_dev, int64_t n, int32_t method, int32_t flags, int32_t *merge,
+                        double *height, int32_t *order, ks_hclust_stats *stats);
+/* Host buffers: validates every argument and every entry before any device
+ * call, then uploads, runs the device entry on the upload and converts. */
+ks_status ks_hclust(ks_ctx *ctx, const double *diss, int64_t n, int32_t method, int32_t *merge, double *height,
+                    int32_t *order);
+/* Cut the tree into groups: host only, no context.  k in 1 .. n groups, or
+ * k = 0 and a height h: k = n - #{s : height[s] <= h}; the heights must then
+ * be non-decreasing (KS_ERR_ARG otherwise; height may be NULL when k > 0).
+ * The first n - k merges are applied.  group[i] in 1 .. k, numbered in order
+ * of first appearance by observation index: observation 0 is in group 1, the
+ * next observation not in group 1 opens group 2, and so on.  With complete
+ * linkage h bounds every group's diameter. */
+ks_status ks_hclust_cut(const int32_t *merge, const double *height, int64_t n, int32_t k, double h, int32_t *group);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

@@ -75,6 +75,14 @@ class DistStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class HclustStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_init", C.c_double),
+                ("ms_merge", C.c_double), ("n", C.c_int64), ("n_rescans", C.c_int64), ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -109,12 +117,15 @@ EXPORTS = [
     "ks_region_spectra", "ks_region_spectra_dev", "ks_spectra_tile_bases",
     "ks_spectra_dist", "ks_spectra_dist_dev", "ks_spectra_cross_dist", "ks_spectra_cross_dist_dev",
     "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
+    "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
 ]
 
 KS_SPECTRA_MAX_Q = 6
 KS_SPECTRA_BOTH_STRANDS = 1
 KS_DIST_MAX_NCOL = 4096
 KS_DIST_SQUARED = 1
+HCLUST_METHODS = {"complete": 0, "single": 1, "average": 2}  # KS_HCLUST_*
+KS_HCLUST_KEEP_INPUT = 1
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -190,6 +201,9 @@ def load():
         "ks_dist_pair_offsets": ([P, P, I64, I64, P], None),
         "ks_dist_tiles_of": ([P, I64, I64, P, P], None),
         "ks_dist_tile_rows": ([], I32),
+        "ks_hclust": ([P, P, I64, I32, P, P, P], I32),
+        "ks_hclust_dev": ([P, P, I64, I32, I32, P, P, P, P], I32),
+        "ks_hclust_cut": ([P, P, I64, I32, D, P], I32),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -318,3 +332,22 @@ def context(device: int = 0) -> Context:
     if ctx is None:
         ctx = _contexts[device] = Context(device)
     return ctx
+
+
+def hclust_n(length: int) -> int:
+    """n of a condensed vector of n(n-1)/2 entries (n >= 2), or an error."""
+    n = (1 + int(np.sqrt(1.0 + 8.0 * length))) // 2
+    for m in (n - 1, n, n + 1):
+        if m >= 2 and m * (m - 1) // 2 == length:
+            return m
+    raise KmerSpansError(f"a condensed vector holds n(n-1)/2 entries for some n >= 2; {length} is no such number")
+
+
+def hclust_method(method) -> int:
+    if method not in HCLUST_METHODS:
+        raise KmerSpansError(f"method must be one of {sorted(HCLUST_METHODS)}, not {method!r}")
+    return HCLUST_METHODS[method]
+
+
+def hclust_outputs(n: int):
+    return np.zeros((n - 1, 2), dtype=np.int32), np.zeros(n - 1, dtype=np.float64), np.zeros(n, dtype=np.int32)

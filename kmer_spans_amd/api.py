@@ -282,6 +282,63 @@ def region_distances(counts, rows=None, rows_b=None, squared: bool = False, devi
     return out
 
 
+def region_hclust(dist, method: str = "complete", device: int = 0) -> dict:
+    """R's hclust() of a condensed dissimilarity vector (test.R:776), run on
+    the device.
+
+    dist: float64[n(n-1)/2], the condensed form region_distances returns (R's
+    dist object, scipy's pdist); n is solved from its length.  Every entry
+    must be finite.  method: "complete" (R's default), "single" or "average".
+    The nearest-neighbour-list agglomeration with every tie going to the
+    lowest index (include/kmer_spans.h): complete and single heights carry the
+    bits of input entries.  Returns {'merge': int32[n-1, 2], 'height':
+    float64[n-1], 'order': int32[n], 'method'} as in R's hclust object:
+    observation i (0-based) is -(i+1), the cluster of step t is t+1, order
+    lists the leaves 1-based from left to right."""
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    if d.ndim != 1:
+        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
+    n = _lib.hclust_n(int(d.size))
+    merge, height, order = _lib.hclust_outputs(n)
+    check(load().ks_hclust(_ctx(device), d.ctypes.data, n, _lib.hclust_method(method), merge.ctypes.data,
+                           height.ctypes.data, order.ctypes.data))
+    return {"merge": merge, "height": height, "order": order, "method": method}
+
+
+def cut_tree(tree_or_merge, height=None, k=None, h=None) -> np.ndarray:
+    """R's cutree(): the groups of a tree from region_hclust, on the host.
+
+    tree_or_merge: the dict region_hclust returns, or its merge table with
+    height=.  Give exactly one of k (the number of groups, 1 .. n) and h (a
+    height: every merge at or below it is applied; the heights must be
+    non-decreasing).  Returns int32[n] group numbers 1 .. k in order of first
+    appearance: observation 0 is in group 1.  With complete linkage h bounds
+    every group's diameter."""
+    if isinstance(tree_or_merge, dict):
+        merge, height = tree_or_merge["merge"], tree_or_merge["height"]
+    else:
+        merge = tree_or_merge
+    if (k is None) == (h is None):
+        raise KmerSpansError("give exactly one of k and h")
+    merge = np.ascontiguousarray(merge, dtype=np.int32)
+    if merge.ndim != 2 or merge.shape[1] != 2:
+        raise KmerSpansError("merge must be an int32 [n-1, 2] table")
+    n = int(merge.shape[0]) + 1
+    hp = None
+    if height is not None:
+        height = np.ascontiguousarray(height, dtype=np.float64)
+        if height.shape != (n - 1,):
+            raise KmerSpansError("height must hold one value per row of merge")
+        hp = height.ctypes.data
+    if k is not None:
+        if int(k) != k or not 1 <= int(k) <= n:
+            raise KmerSpansError(f"k = {k} is not in 1 .. n = {n}")
+    group = np.zeros(n, dtype=np.int32)
+    check(load().ks_hclust_cut(merge.ctypes.data, hp, n, int(k) if k is not None else 0,
+                               float(h) if h is not None else 0.0, group.ctypes.data))
+    return group
+
+
 # ------------------------------------------------------------ table builders
 
 def _table(fn, counts, k):

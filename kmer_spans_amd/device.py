@@ -451,3 +451,29 @@ def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=
         check(load().ks_spectra_cross_dist_dev(h, C.c_void_p(counts.data_ptr()), n, ncol, ptr(ra), na, ptr(rb),
                                                int(rb.numel()), flags, ptr(res), C.byref(st)))
     return res, st.as_dict()
+
+
+def region_hclust(ctx: _lib.Context, dist: torch.Tensor, method: str = "complete", keep_input: bool = True):
+    """ks_hclust_dev: agglomerative clustering (R's hclust) of the condensed
+    distances region_distances returns, on the device.
+
+    dist: a contiguous float64 CUDA tensor of n(n-1)/2 entries, n >= 2, every
+    entry finite (a NaN from an empty spectrum row is an error naming its
+    offset; the tensor is untouched then).  method: "complete" (R's default),
+    "single" or "average".  keep_input=True clusters a device copy and leaves
+    dist's bits unchanged; keep_input=False updates dist in place and consumes
+    it.  Returns (tree, stats): tree is a dict of merge int32 [n-1, 2], height
+    float64 [n-1], order int32 [n] (numpy, as R's hclust object: observation i
+    is -(i+1), step t is t+1, order is 1-based) and method; stats the dict of
+    ks_hclust_stats."""
+    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
+            or not dist.is_contiguous()):
+        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
+    n = _lib.hclust_n(int(dist.numel()))
+    merge, height, order = _lib.hclust_outputs(n)
+    st = _lib.HclustStats()
+    _order(ctx)
+    check(load().ks_hclust_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n,
+                               _lib.hclust_method(method), _lib.KS_HCLUST_KEEP_INPUT if keep_input else 0,
+                               merge.ctypes.data, height.ctypes.data, order.ctypes.data, C.byref(st)))
+    return {"merge": merge, "height": height, "order": order, "method": method}, st.as_dict()
