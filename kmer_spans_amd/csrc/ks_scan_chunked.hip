@@ -1920,8 +1920,8 @@ constexpr int kLdsTableK = 7;
 // index, so it and the chunk aggregates fit int32 (|S| <= 2^28) and equal the
 // FP64 chain exactly; 32-bit integer compares and selects instead of FP64
 // ones (half the VALU work of this ALU-bound pass), the table as int32 in
-// LDS (64 KiB at k = 7: two blocks per CU).  Outputs as k_pass1_lds<false,
-// true> (FP64 aggregates, no |s| sum, no non-finite flag).
+// LDS (64 KiB at k = 7: two blocks per CU).  Outputs as k_pass1_lds<false>
+// without the |s| sum and the non-finite flag (FP64 aggregates).
 __global__ void __launch_bounds__(1024) k_pass1_lds_int(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
                                                         uint32_t *__restrict__ visits, P1 o, Cand cand) {
   __shared__ int32_t s_val[1 << (2 * kLdsTableK)];
@@ -1995,10 +1995,9 @@ __global__ void __launch_bounds__(1024) k_pass1_lds_int(Chunks g, int64_t total,
   }
 }
 
-// kExact (integer tables, k_carry_exact): no |s| sum and no non-finite flag
-// (neither is read on that path; two of the ~30 VALU ops per index of this
-// ALU-bound pass)
-template <bool kTrlr, bool kExact = false>
+// (integer tables on the exact carry take k_pass1_lds_int instead: neither the
+// |s| sum nor the non-finite flag is read on that path)
+template <bool kTrlr>
 __global__ void __launch_bounds__(1024) k_pass1_lds(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
                                                     uint32_t *__restrict__ visits, P1 o, Cand cand,
                                                     const double *__restrict__ xh, SummP1 sp) {
@@ -2070,10 +2069,8 @@ __global__ void __launch_bounds__(1024) k_pass1_lds(Chunks g, int64_t total, int
         pmin = asum < pmin ? asum : pmin;
         parg = asum > pmax ? i : parg;
         pmax = asum > pmax ? asum : pmax;
-        if (!kExact) {
-          sabs += fabs(s);
-          special |= !isfinite(s);
-        }
+        sabs += fabs(s);
+        special |= !isfinite(s);
         const double tt = prev + s;
         const double S = tt > 0 ? tt : 0.0;
         const bool open = (prev == 0) & (S > 0);
@@ -2529,14 +2526,6 @@ __global__ void __launch_bounds__(256) k_ascan_apply(const int64_t *__restrict__
 // Largest value of the predicted trajectory that keeps a binade summary
 // meaningful; below kLMin the trajectory crosses binades every few steps.
 constexpr double kLMin = 64.0;
-
-// Carried chunks without a usable summary are replayed wave-parallel
-// (replay_par) when its speculation verifies, else serially.
-#ifdef KS_NO_PAR_REPLAY
-constexpr bool kParReplay = false;
-#else
-constexpr bool kParReplay = true;
-#endif
 
 // Summary of each chunk for the binade of its predicted trajectory (lane per
 // chunk, full occupancy); chunks predicted to leave the binade or to approach
@@ -3325,7 +3314,7 @@ __device__ __forceinline__ void carry_segment(const Chunks &g, int64_t c0, int64
         }
         double T = x, hmax = -1.0;
         int hq = -1, harg = 0;
-        const bool par = kParReplay && replay_par(v, n, x, T, hmax, harg);
+        const bool par = replay_par(v, n, x, T, hmax, harg);
         if (par) n_par += 1;
         for (int i = 0; i < 64 && hq < 0 && !par; ++i) {
           if (4 * i >= n) break;
@@ -4034,936 +4023,816 @@ __global__ void k_candidates(Chunks g, const int64_t *__restrict__ ra, const int
 
 }  // namespace
 
-// KS_DEBUG_VERIFY=1 (diagnostics): after a chunked scan of a small input
-// (<= 64 Mi bases, k <= 11, kmer_regions mode), the device's packed codes,
-// chunk layout, pass-1 results and carry modes are copied back and checked
-// against a host recomputation from the sequence bytes and the base table;
-// every mismatch goes to stderr with its chunk and both values.  Reads the
-// buffers after the call's last kernel, so a value that is right here but was
-// wrong when a kernel read it points at an ordering edge, one that is wrong
-// here at the kernel that wrote it.
-static void debug_verify(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int k, const TableView &tv,
-                         const Chunks &g, const P1 &p1, const Carry &cr, bool exact, int trlr) {
-  const int64_t nch = g.nch;
-  if (trlr || k > 11 || total > ((int64_t)64 << 20) || nch <= 0) return;
-  (void)hipDeviceSynchronize();
-  auto get = [&](auto *dst, const void *src, size_t n) {
-    if (n) (void)hipMemcpy(dst, src, n * sizeof(*dst), hipMemcpyDeviceToHost);
-  };
-  std::vector<uint8_t> seq((size_t)total);
-  get(seq.data(), s->seq, (size_t)total);
-  const int64_t nk = (int64_t)1 << (2 * k);
-  std::vector<double> val((size_t)nk);
-  if (tv.compressed) {
-    std::vector<uint16_t> codes((size_t)nk);
-    get(codes.data(), tv.codes, (size_t)nk);
-    std::vector<double> lut((size_t)std::max(tv.nlut, 1));
-    get(lut.data(), tv.lut, (size_t)tv.nlut);
-    for (int64_t i = 0; i < nk; ++i) val[i] = lut[codes[i]];
-  } else {
-    get(val.data(), tv.vals, (size_t)nk);
-  }
-  long long bad = 0;
-  auto report = [&](const char *what, int64_t c, double got, double want) {
-    if (++bad <= 12)
-      fprintf(stderr, "[verify] chunk %lld of %lld: %s = %.17g, host %.17g\n", (long long)c, (long long)nch, what, got,
-              want);
-  };
-  std::vector<int64_t> start((size_t)nch);
-  std::vector<int32_t> n((size_t)nch), run((size_t)nch), tbeg((size_t)nch), targ((size_t)nch);
-  std::vector<double> cexit((size_t)nch), tmax((size_t)nch), cx((size_t)nch);
-  std::vector<uint8_t> mode((size_t)nch);
-  get(start.data(), g.start, (size_t)nch);
-  get(n.data(), g.n, (size_t)nch);
-  if (g.packed) {  // the words the chunks read (a part's run pass packs its own range only)
-    const int64_t nw = total / 16 + 1;
-    std::vector<uint32_t> pk((size_t)nw);
-    std::vector<uint8_t> used((size_t)nw, 0);
-    for (int64_t c = 0; c < nch; ++c)
-      for (int64_t w = std::max<int64_t>(0, (start[c] - k) / 16); w <= (start[c] + n[c]) / 16 && w < nw; ++w) used[w] = 1;
-    get(pk.data(), g.packed, (size_t)nw);
-    for (int64_t w = 0; w < nw; ++w) {
-      uint32_t want = 0;
-      for (int q = 0; q < 16; ++q) want |= enc(16 * w + q < total ? seq[16 * w + q] : (uint8_t)'N') << (30 - 2 * q);
-      if (used[w] && pk[w] != want && 16 * w + 16 <= total) report("packed word", w, (double)pk[w], (double)want);
-    }
-  }
-  get(run.data(), g.run, (size_t)nch);
-  get(tbeg.data(), p1.tbeg, (size_t)nch);
-  get(targ.data(), p1.targ, (size_t)nch);
-  get(cexit.data(), p1.cexit, (size_t)nch);
-  get(tmax.data(), p1.tmax, (size_t)nch);
-  get(cx.data(), cr.x, (size_t)nch);
-  get(mode.data(), cr.mode, (size_t)nch);
-  const uint64_t kmask = (uint64_t)nk - 1;
-  for (int64_t c = 0; c < nch; ++c) {
-    // clean trajectory from 0 over indices start .. start + n - 1 (k-mer
-    // ending at index - 1), as P1Lane::step
-    double prev = 0.0, best = 0.0;
-    int beg = -1, arg = 0;
-    for (int i = 0; i < n[c]; ++i) {
-      const int64_t p = start[c] + i;
-      uint64_t code = 0;
-      for (int64_t q = p - k; q < p; ++q) code = ((code << 2) | enc(seq[q])) & kmask;
-      const double sv = val[code];
-      const double tt = prev + sv;
-      const double S = tt > 0 ? tt : 0.0;
-      const bool open = (prev == 0) & (S > 0), close = (prev > 0) & (S == 0);
-      const bool up = open | (S > best);
-      best = up ? S : best;
-      arg = up ? i : arg;
-      beg = open ? i : (close ? -1 : beg);
-      prev = S;
-    }
-    auto ne = [](double a, double b) { return memcmp(&a, &b, 8) != 0; };
-    if (ne(cexit[c], prev)) report("clean exit", c, cexit[c], prev);
-    if (prev > 0) {
-      if (tbeg[c] != beg) report("tail begin", c, tbeg[c], beg);
-      if (targ[c] != arg) report("tail argmax", c, targ[c], arg);
-      if (ne(tmax[c], best)) report("tail max", c, tmax[c], best);
-    } else if (tbeg[c] != -1) {
-      report("tail begin (none)", c, tbeg[c], -1);
-    }
-    const bool first = c == 0 || run[c - 1] != run[c];
-    if (first && (mode[c] != kModeClean || cx[c] != 0.0)) report("run-first chunk carry mode", c, mode[c], kModeClean);
-  }
-  (void)exact;
-  if (bad) fprintf(stderr, "[verify] %lld mismatches in %lld chunks (k %d, %lld bases)\n", bad, (long long)nch, k,
-                   (long long)total);
+// ------------------------------------------------------------ host driver
+//
+// scan_chunked reads top to bottom: plan (plan_scan: which path the call
+// takes) -> workspace (carve) -> layout kernels -> predictor -> pass 1 ->
+// post-processing and rescans per half -> counter read-back -> retry
+// decisions.  The helpers before it launch; none of them decides a path.
+namespace {
+
+// Slots of ks_ctx::ev this file records (chunked_phase_times reads the phase marks).
+enum : int {
+  kEvBegin = 7,         // phase mark: layout kernels begin
+  kEvP1Begin = 8,       // phase mark: layout and predictor issued, pass 1 begins
+  kEvP1End = 9,         // phase mark: end of pass 1 (the later of the halves)
+  kEvCandEnd = 10,      // phase mark: the last half's candidates emitted
+  kEvEnd = 11,          // phase mark: rescans issued
+  kEvP1Half0 = 12,      // two parts: half 0's pass 1 done (hi); one part: the tail launch's fork (main)
+  kEvSideDone = 13,     // side stream's work done: one part the tail launch, two parts half 1's post-processing
+  kEvP2End = 14,        // phase mark: the last half's prediction and summaries
+  kEvP34End = 15,       // phase mark: the last half's carry and heads
+  kEvPredictFork = 16,  // side forked off main for half 1's predictor
+  kEvP1Fork = 17,       // hi (and side, unless forked already) forked off main for pass 1
+  kEvP1Side = 18,       // side stream's pass 1 done
+};
+
+// One kernel launch, checked.
+template <class... KA, class... A>
+ks_status launch(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t strm, const A &...a) {
+  hipLaunchKernelGGL(kern, grid, block, lds, strm, a...);
+  KS_HIP(hipGetLastError());
+  return KS_OK;
 }
 
-ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, const RunLayout &lay, int k,
-                       const TableView &tv, uint64_t mw, double min_score, uint32_t *visits,
-                       uint32_t *visits_rescan, const RegionBuf &rb, ks_scan_stats *stats, const ScanMode &mode) {
-  const EmitCfg ec{mode.trlr, mw, min_score, mode.min_len, mode.ks, k};
-  hipStream_t st = ctx->stream;
-  const int64_t total = s->offsets_host[s->nseq];
-  const int64_t nruns = runs.n;
-  const int64_t nch = lay.nch, ntiles = lay.ntiles;
-  ctx->chunked_events = false;
-  if (nruns == 0 || nch == 0) return KS_OK;
-  const int64_t *d_cbase = lay.cbase, *d_tbase = lay.tbase;
-  const bool comp = tv.compressed != 0;
+// Run-time value -> template argument: f(std::integral_constant<int, v>) for
+// v in [Lo, Hi], every other value as Def; f(std::true_type / false_type).
+template <int Lo, int Hi, int Def, class F>
+ks_status pick_int(int v, F &&f) {
+  if constexpr (Lo > Hi) {
+    return f(std::integral_constant<int, Def>{});
+  } else {
+    if (v == Lo) return f(std::integral_constant<int, Lo>{});
+    return pick_int<Lo + 1, Hi, Def>(v, f);
+  }
+}
+template <class F>
+ks_status pick_bool(bool v, F &&f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
 
-  // ---- workspace
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const int64_t nwin = (nch + 63) / 64;
+// A part of the runs: chunks [c0, c1), runs [r0, r1), stitch tiles [t0, t1).
+struct Half {
+  int64_t c0, c1, r0, r1, t0, t1;
+};
+
+enum class P1Family {
+  Lds,           // small k: the whole table in LDS, persistent blocks, no code store (k_pass1_lds / _int)
+  Line,          // line tables: every chunk, a lane's bases from guarded loads (k_pass1l / k_pass1w / k_pass1r<3>)
+  F64Expanded,   // FP64 expanded table, weighted rank (k_pass1pf + tail launch, or k_pass1r<1|2> alone)
+  CompExpanded,  // expanded table on the pipelined pass (k_pass1p + tail launch)
+  Plain,         // unexpanded table (k_pass1<1, ...>; a compressed one with the code store)
+};
+
+// Everything a call's path depends on, decided once (plan_scan).
+struct ScanPlan {
+  P1Family family;
+  bool comp;       // compressed table
+  bool lds_table;  // k <= kLdsTableK on packed bases (KS_NO_LDS_TABLE: off)
+  // Integer tables: the exact carry (k_carry_exact) needs no predictor and no
+  // summaries (KS_NO_EXACT: the general path, for A/B runs and tests).  Only
+  // on the table forms of the pipelined passes -- LDS, line, expanded; an
+  // unexpanded table of another size takes the code-store pass and
+  // k_summaries.  Exact while every partial sum of a run is: |s| <= 2^20 over
+  // fewer than 2^32 indices stays below 2^52.  KS_TEST_SEG_FALLBACK, which
+  // forces the general carry's per-run fallback, takes the general path.
+  bool exact;
+  // Pass 1 writes the binade summaries itself (no per-position code store):
+  // small k from the LDS-staged table (k_summaries after the prescan took 13.3
+  // vs 8.8 ms at k = 7 log2); compressed expanded and line tables; FP64 tables
+  // only with KS_F64_P1SUMM=1 (lines, expanded J 2..4).  Needs packed bases
+  // and the binade predictor (a table without one is scanned unexpanded).
+  bool p1summ;
+  // No chunk summaries at all: KS_NO_SUMMARIES, and FP64 tables unless
+  // KS_F64_P1SUMM is set (=0: k_summaries).  A summary serves a chunk only
+  // while its carry-in stays >= 64 in one binade; weighted rank values in
+  // [-0.5, 0.5] keep the carry far below that: 5,598 of 11.96 M chunks at
+  // config 3 were summary-served, 1.0 M replayed.  At k = 15 50.6 vs 53.7 ms
+  // with k_pass1pf's pass-1 summaries and 59.4 with k_summaries, at k = 13
+  // 29.8 vs 30.2 with k_summaries (profiles/r5/ab/ab_nosumm_*.txt).
+  bool no_summ;
+  bool lds_lut;     // compressed: the LUT fits the LDS copy of the streaming passes
+  bool need_codes;  // per-index code store (uint16 per scan index): written by the compressed
+                    // unexpanded pass 1 for k_summaries
+  int J;            // expansion of the table as pass 1 and the heads read it (compressed tables are
+                    // scanned expanded only on the summarising or exact pass)
+  int force_fb;     // KS_TEST_SEG_FALLBACK (tests): force the carry's per-run fallback
+  bool epoch_stale; // KS_TEST_EPOCH_STALE (tests): the post-processing expects another epoch than pass
+                    // 1 stamped -- what it would see reading an earlier call's pass-1 results -- so
+                    // the epoch guard must fail the call
+  bool rank_alone;  // F64Expanded: the weighted-rank code lines in one launch (k = 14 / 15: J = 4 / 3
+                    // per 128-B line read against 3 / 2 per FP64 expanded entry); every chunk
+  bool tail;        // the family launches the last chunks apart: k_pass1p / k_pass1pf leave the chunks
+                    // whose reads could pass the end of the buffer (chunk starts increase with the
+                    // chunk index, so they are among the last kP1TailMargin + CH chunks) to k_pass1
+  int64_t ctail;    // first chunk of the tail launch
+  // Two halves of the runs (pass-1-summary path): the second half's pass 1
+  // (side stream) runs while the first half's latency-bound later passes
+  // (carry, stitch) run on the main stream; halves split at a run boundary, so
+  // no carry or stitch crosses it.  One part where it measured no slower:
+  //  - without pass-1 summaries.  FP64 line tables (weighted rank): the two
+  //    pass-1 launches ran side by side and ended together (15.2 ms each,
+  //    profiles/r5/rank/step_timeline_rank_k13_twopart.txt), so the first
+  //    part's post-processing never ran under the second's pass 1: 27.75 vs
+  //    28.56 ms in one part (profiles/r5/ab/ab_nosplit_k13.txt).  FP64 expanded
+  //    tables: two parts 52.1 vs 51.6 ms at k = 15, 46.0 vs 44.8 at k = 14
+  //    (profiles/r5/ab/ab_nosumm_split_k15.txt, ab_nosumm_k14.txt).  The exact
+  //    carry's post-processing is short: two parts measured the same at lower
+  //    run-to-run spread, 6.44 vs 6.55 ms median at k = 7
+  //    (profiles/r4/ab3/ab_k7pm1_exact_split.txt).
+  //  - below ~2 M chunks, ~500 Mbp: at the 8-way shard, 1.5 M chunks, 2.38 vs
+  //    2.42 ms in-process; 4-way, 3 M chunks, two parts 4.24 vs 4.37
+  //    (profiles/r5/ab/ab_one_part_*.txt).  KS_SPLIT_MIN_CHUNKS: the threshold
+  //    -- tests set 0 to run the two-part path on small genomes.
+  bool split;
+  int nhalf;
+  Half half[2];
+  bool debug_carry, debug_verify;  // KS_DEBUG_CARRY, KS_DEBUG_VERIFY (diagnostics; read once per process)
+};
+
+// The plan of one call.  Reads every KS_* switch of this file (per call: tests
+// set them in-process between calls); makes no HIP call.
+ScanPlan plan_scan(const TableView &tv, int k, const ScanMode &mode, const Runs &runs, const RunLayout &lay) {
+  static const bool debug_carry = getenv("KS_DEBUG_CARRY") != nullptr;
+  static const bool debug_verify = getenv("KS_DEBUG_VERIFY") != nullptr;
+  const char *f64e = getenv("KS_F64_P1SUMM");
+  const char *smin = getenv("KS_SPLIT_MIN_CHUNKS");
+  const int64_t split_min = smin ? atoll(smin) : ((int64_t)2 << 20);
+  const bool packed = runs.packed != nullptr;
+  const int Jt = tv.ext != nullptr ? tv.ext_J : 1;
+  const int64_t nch = lay.nch;
+
+  ScanPlan p{};
+  p.debug_carry = debug_carry;
+  p.debug_verify = debug_verify;
+  p.comp = tv.compressed != 0;
+  p.lds_table = k <= kLdsTableK && packed && getenv("KS_NO_LDS_TABLE") == nullptr;
+  const bool line = tv.line != nullptr && !p.lds_table && packed;
+  const bool f64_summ = !p.comp && !p.lds_table && f64e && atoi(f64e) != 0 && (line || (Jt >= 2 && Jt <= 4));
+  p.force_fb = getenv("KS_TEST_SEG_FALLBACK") != nullptr ? 1 : 0;
+  p.epoch_stale = getenv("KS_TEST_EPOCH_STALE") != nullptr;
+  p.exact = tv.exact && !mode.trlr && packed && (p.lds_table || line || Jt >= 2) &&
+            lay.longest < ((int64_t)1 << 32) && !p.force_fb && getenv("KS_NO_EXACT") == nullptr;
+  p.no_summ = getenv("KS_NO_SUMMARIES") != nullptr || (!p.comp && !p.lds_table && !f64e);
+  p.p1summ = !p.exact && (p.lds_table || (p.comp ? (Jt >= 2 || line) : f64_summ)) && packed && tv.approx != nullptr;
+  p.need_codes = p.comp && !p.p1summ && !p.exact && !p.lds_table;
+  p.lds_lut = p.comp && tv.nlut <= kLdsLutMax;
+  p.J = (tv.ext != nullptr && (p.p1summ || p.exact || !p.comp)) ? tv.ext_J : 1;
+
+  p.ctail = nch > 1024 ? nch - 1024 : 0;
+  p.split = p.p1summ && nch > split_min && lay.split_r > 0 && lay.split_r < runs.n && lay.split_c >= 1024 &&
+            lay.split_c + 1024 <= p.ctail;
+  p.nhalf = p.split ? 2 : 1;
+  p.half[0] = Half{0, nch, 0, runs.n, 0, lay.ntiles};
+  if (p.split) {
+    p.half[0] = Half{0, lay.split_c, 0, lay.split_r, 0, lay.split_t};
+    p.half[1] = Half{lay.split_c, nch, lay.split_r, runs.n, lay.split_t, lay.ntiles};
+  }
+
+  if (p.lds_table)
+    p.family = P1Family::Lds;
+  else if (line && (p.p1summ || p.exact || !p.comp))
+    p.family = P1Family::Line;
+  else if (!p.comp && p.J >= 2 && p.J <= 4 && packed)
+    p.family = P1Family::F64Expanded;
+  else if (p.p1summ || p.exact)
+    p.family = P1Family::CompExpanded;
+  else
+    p.family = P1Family::Plain;
+  p.rank_alone = p.family == P1Family::F64Expanded && tv.rline && !mode.trlr && !p.p1summ && !p.split &&
+                 (k == 14 || k == 15);
+  p.tail = (p.family == P1Family::F64Expanded && !p.rank_alone) || p.family == P1Family::CompExpanded;
+  return p;
+}
+
+// Bump carver over one allocation: take<T>(n) hands out n elements of T on a
+// 256-byte boundary.  Without a base it only sizes (and returns null).
+struct Carver {
+  char *base;
   size_t off = 0;
-  const size_t o_start = off; off += al(nch * 8);
-  const size_t o_n = off; off += al(nch * 4);
-  const size_t o_run = off; off += al(nch * 4);
-  const size_t o_p1d = off; off += al(nch * 8 * 6);
-  const size_t o_p1i = off; off += al(nch * 4 * 3);
-  const size_t o_spec = off; off += al(nch);
-  const size_t o_ep = off; off += al(nch * 4);
-  const size_t o_xt = off; off += al(nch * 8);
-  const size_t o_se = off; off += al(nch * 4);
-  const size_t o_sD = off; off += al(nch * 8 * 6);
-  const size_t o_sA = off; off += al(nch * 4 * 2);
-  const size_t o_x = off; off += al(nch * 8);
-  const size_t o_mode = off; off += al(nch);
-  const size_t o_hq = off; off += al(nch * 4 * 2);
-  const size_t o_hmax = off; off += al(nch * 8);
-  const size_t o_cnt = off; off += al(8 * (5 * kSegs + 8));  // + the region counters' copy, half 1's lists
-  const size_t o_flag = off; off += al(nch + 64);
-  const size_t o_xagg = off; off += al(ntiles * 32) * 2;
+  template <class T>
+  T *take(size_t n) {
+    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+    off += (n * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+};
+
+// The call's buffers: SLOT_CHUNK_A carved (carve), the code store, the
+// candidate and rescan lists of each half, the diagnostics' counters.
+struct Work {
+  Chunks g;
+  P1 p1;
+  double *xt;  // predicted entries (P2 prescan)
+  Summ sm;
+  Carry cr;
+  // cnts: [0, kSegs) candidate counters, [kSegs, 2 kSegs) rescan counters,
+  // [2 kSegs + 2h] replays, [2 kSegs + 2h + 1] error bits (u32) of half h,
+  // [2 kSegs + 8, 3 kSegs + 8) the region counters' copy, [3 kSegs + 8,
+  // 5 kSegs + 8) the second half's candidate and rescan counters
+  unsigned long long *cnts;
+  uint8_t *flag;
+  XTiles xagg, xtin;
   // pass-1 summaries: predictor sums / exits / zero flags, predicted entries,
-  // the summaries, the fix list
-  const size_t o_pa = off; off += al(nch * 8);
-  const size_t o_pb = off; off += al(nch * 8);
-  const size_t o_pz = off; off += al(nch);
-  const size_t o_xh = off; off += al(nch * 8);
-  const size_t o_spe = off; off += al(nch * 4 * 2);
-  const size_t o_spd = off; off += al(nch * 8 * 6);
-  const size_t o_spa = off; off += al(nch * 4 * 2);
-  const size_t o_fix = off; off += al(nch * 8 + 16);
-  const size_t o_ssel = off; off += al(nch);  // Summ::sel
-  const size_t o_tagg = off; off += al(ntiles * 16);  // parallel approximate scan: tile maps, tile entries
-  const size_t o_tin = off; off += al(ntiles * 8);
-  const size_t o_trun = off; off += al(ntiles * 4 + 4);  // stitch tile -> run (k_tile_runs)
+  // the summaries, the fix list (nfix[2]: one counter per half)
+  double *pa, *pb;
+  uint8_t *pz;
+  double *xh;
+  SummP1 sp1;
+  unsigned long long *nfix;
+  int64_t *fix;
+  double2 *tagg;  // parallel approximate scan: tile maps, tile entries
+  double *tin;
+  int32_t *trun;  // stitch tile -> run (k_tile_runs)
+  TileComp tcomp;
+  ReplayBuf rpb;  // likely-replay prefetch (k_marks_select lists, k_summ_fixw fills)
+  uint16_t *codes = nullptr;  // ScanPlan::need_codes
+  // Candidates and rescans in one list per half: the first half's are
+  // emitted and rescanned while the second half is post-processed (a list
+  // cannot be read while the other half's pass 1 still appends to it).
+  Cand cands[2];
+  Rescan rss[2];
+  long long *dbg = nullptr;  // KS_DEBUG_CARRY: 9 counters per 64-chunk window + 4
+  int64_t nwin = 0;
+};
+
+// SLOT_CHUNK_A's layout.  base null: the size alone.
+Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const uint32_t *packed, size_t *bytes) {
+  Carver cv{base};
+  int64_t *start = cv.take<int64_t>(nch);
+  int32_t *n = cv.take<int32_t>(nch);
+  int32_t *run = cv.take<int32_t>(nch);
+  double *p1d = cv.take<double>(nch * 6);
+  int32_t *p1i = cv.take<int32_t>(nch * 3);
+  uint8_t *spec = cv.take<uint8_t>(nch);
+  uint32_t *ep = cv.take<uint32_t>(nch);
+  double *xt = cv.take<double>(nch);
+  int32_t *se = cv.take<int32_t>(nch);
+  long long *sD = cv.take<long long>(nch * 6);
+  int32_t *sA = cv.take<int32_t>(nch * 2);
+  double *x = cv.take<double>(nch);
+  uint8_t *cmode = cv.take<uint8_t>(nch);
+  int32_t *hq = cv.take<int32_t>(nch * 2);
+  double *hmax = cv.take<double>(nch);
+  unsigned long long *cnts = cv.take<unsigned long long>(5 * kSegs + 8);  // + the region counters' copy, half 1's lists
+  uint8_t *flag = cv.take<uint8_t>(nch + 64);
+  char *xa0 = cv.take<char>(ntiles * 32), *xa1 = cv.take<char>(ntiles * 32);
+  double *pa = cv.take<double>(nch);
+  double *pb = cv.take<double>(nch);
+  uint8_t *pz = cv.take<uint8_t>(nch);
+  double *xh = cv.take<double>(nch);
+  int32_t *spe = cv.take<int32_t>(nch * 2);
+  long long *spd = cv.take<long long>(nch * 6);
+  int32_t *spa = cv.take<int32_t>(nch * 2);
+  unsigned long long *nfix = cv.take<unsigned long long>(nch + 2);  // [2] counters, then the list
+  uint8_t *ssel = cv.take<uint8_t>(nch);  // Summ::sel
+  double2 *tagg = cv.take<double2>(ntiles);
+  double *tin = cv.take<double>(ntiles);
+  int32_t *trun = cv.take<int32_t>(ntiles + 1);
   const int64_t ngt = nch / 64 + 2;  // global 64-chunk tiles (carry tile batches)
-  const size_t o_gte = off; off += al(ngt * 4);
-  const size_t o_gtd = off; off += al(ngt * 8 * 6);
-  const size_t o_gtm = off; off += al(ngt * 8);
-  const size_t o_gtee = off; off += al(ngt * 4);
-  // likely-replay prefetch (k_marks_select lists, k_summ_fixw fills)
-  const int64_t rcap_h = std::max<int64_t>(65536, nch / 128);  // slots per half
-  const size_t o_rslot = off; off += al(nch * 4);
-  const size_t o_rchunk = off; off += al(2 * rcap_h * 8);
-  const size_t o_rcnt = off; off += al(64);
-  const size_t o_rval = off; off += al(2 * rcap_h * 256 * 8);
-  void *wsp = nullptr;
-  KS_TRY(ensure(ctx, SLOT_CHUNK_A, off, &wsp));
-  char *W = static_cast<char *>(wsp);
-  Chunks g{reinterpret_cast<int64_t *>(W + o_start), reinterpret_cast<int32_t *>(W + o_n),
-           reinterpret_cast<int32_t *>(W + o_run), nch, runs.packed};
-  double *p1d = reinterpret_cast<double *>(W + o_p1d);
-  int32_t *p1i = reinterpret_cast<int32_t *>(W + o_p1i);
-  P1 p1{p1d, p1d + nch, p1d + 2 * nch, p1d + 3 * nch, p1d + 4 * nch, p1d + 5 * nch, p1i, p1i + nch,
-        reinterpret_cast<uint8_t *>(W + o_spec), p1i + 2 * nch};
-  p1.ep = reinterpret_cast<uint32_t *>(W + o_ep);
-  p1.epoch = ++ctx->scan_epoch;
-  double *xt = reinterpret_cast<double *>(W + o_xt);
-  long long *sD = reinterpret_cast<long long *>(W + o_sD);
-  Summ sm{reinterpret_cast<int32_t *>(W + o_se), sD, sD + 2 * nch, sD + 4 * nch,
-          reinterpret_cast<int32_t *>(W + o_sA)};
-  int32_t *hqp = reinterpret_cast<int32_t *>(W + o_hq);
-  Carry cr{reinterpret_cast<double *>(W + o_x), reinterpret_cast<uint8_t *>(W + o_mode), hqp,
-           reinterpret_cast<double *>(W + o_hmax), hqp + nch};
-  unsigned long long *cnts = reinterpret_cast<unsigned long long *>(W + o_cnt);
-  uint8_t *d_flag = reinterpret_cast<uint8_t *>(W + o_flag);
+  int32_t *gte = cv.take<int32_t>(ngt);
+  long long *gtd = cv.take<long long>(ngt * 6);
+  long long *gtm = cv.take<long long>(ngt);
+  int32_t *gtee = cv.take<int32_t>(ngt);
+  const int64_t rcap_h = std::max<int64_t>(65536, nch / 128);  // replay slots per half
+  int32_t *rslot = cv.take<int32_t>(nch);
+  int64_t *rchunk = cv.take<int64_t>(2 * rcap_h);
+  unsigned long long *rcnt = cv.take<unsigned long long>(8);
+  double *rval = cv.take<double>(2 * rcap_h * 256);
+  *bytes = cv.off;
+
+  Work w{};
+  if (!base) return w;
+  w.g = Chunks{start, n, run, nch, packed};
+  w.p1 = P1{p1d, p1d + nch, p1d + 2 * nch, p1d + 3 * nch, p1d + 4 * nch, p1d + 5 * nch, p1i, p1i + nch, spec,
+            p1i + 2 * nch};
+  w.p1.ep = ep;
+  w.xt = xt;
+  w.sm = Summ{se, sD, sD + 2 * nch, sD + 4 * nch, sA};
+  w.cr = Carry{x, cmode, hq, hmax, hq + nch};
+  w.cnts = cnts;
+  w.flag = flag;
   auto xtiles = [&](char *p) {
     return XTiles{reinterpret_cast<int32_t *>(p), reinterpret_cast<int32_t *>(p) + ntiles,
                   reinterpret_cast<long long *>(p + ntiles * 8), reinterpret_cast<long long *>(p + ntiles * 16),
                   reinterpret_cast<double *>(p + ntiles * 24)};
   };
-  const XTiles xagg = xtiles(W + o_xagg), xtin = xtiles(W + o_xagg + al(ntiles * 32));
-  double2 *d_tagg = reinterpret_cast<double2 *>(W + o_tagg);
-  int32_t *d_trun_map = reinterpret_cast<int32_t *>(W + o_trun);
-  int32_t *d_trun = d_trun_map;
-  long long *gtd = reinterpret_cast<long long *>(W + o_gtd);
-  const TileComp tcomp{reinterpret_cast<int32_t *>(W + o_gte), gtd, gtd + 2 * ngt, gtd + 4 * ngt,
-                       reinterpret_cast<long long *>(W + o_gtm), reinterpret_cast<int32_t *>(W + o_gtee)};
-  ReplayBuf rpb{reinterpret_cast<int32_t *>(W + o_rslot), reinterpret_cast<int64_t *>(W + o_rchunk),
-                reinterpret_cast<double *>(W + o_rval), reinterpret_cast<unsigned long long *>(W + o_rcnt), rcap_h};
-  double *d_tin = reinterpret_cast<double *>(W + o_tin);
-  // approximate max-plus scan of (sum, clean exit) over runs [r0, r1) (tiles
-  // [t0, t1)): three parallel kernels (the one-wave-per-run k_approx_scan when
-  // the range has no tile)
-  // waves per block of the wave-per-tile / wave-per-window kernels (A/B: 2 of 1-4)
-  constexpr int wpb = 2;
-  auto ascan = [&](const P1 &o, double *out, int64_t r0, int64_t r1, int64_t t0, int64_t t1,
-                   hipStream_t strm) -> ks_status {
-    if (r1 <= r0) return KS_OK;
-    if (t1 <= t0) {
-      hipLaunchKernelGGL(k_approx_scan, dim3((unsigned)(r1 - r0)), dim3(64), 0, strm, d_cbase, r1, o, out, r0);
-      KS_HIP(hipGetLastError());
-      return KS_OK;
+  w.xagg = xtiles(xa0);
+  w.xtin = xtiles(xa1);
+  w.pa = pa;
+  w.pb = pb;
+  w.pz = pz;
+  w.xh = xh;
+  w.sp1 = SummP1{spe, spd, spd + 2 * nch, spd + 4 * nch, spa};
+  w.nfix = nfix;
+  w.fix = reinterpret_cast<int64_t *>(nfix + 2);
+  w.tagg = tagg;
+  w.tin = tin;
+  w.trun = trun;
+  w.tcomp = TileComp{gte, gtd, gtd + 2 * ngt, gtd + 4 * ngt, gtm, gtee};
+  // (the carry reads no replay slots unless k_marks_select wrote them)
+  w.rpb = ReplayBuf{plan.p1summ ? rslot : nullptr, rchunk, rval, rcnt, rcap_h};
+  // pass-1 summaries are read where pass 1 wrote them (summ_at): the selection
+  // writes a byte per chunk instead of copying 56 (metric step 14.47 vs 14.61 ms
+  // median in-process, profiles/r4/ab4/ab_copy_log2.txt)
+  if (plan.p1summ) {
+    w.sm.sel = ssel;
+    w.sm.pD = w.sp1.D;
+    w.sm.pM = w.sp1.M;
+    w.sm.pN = w.sp1.N;
+    w.sm.pA = w.sp1.A;
+  }
+  w.nwin = (nch + 63) / 64;
+  return w;
+}
+
+// One call's inputs, as the launches take them.
+struct ScanCall {
+  ks_ctx *ctx;
+  const ks_dev_seqs *s;
+  int64_t total;
+  int k;
+  const TableView &tv;
+  const EmitCfg ec;
+  const Runs &runs;
+  const RunLayout &lay;
+  const RegionBuf &rb;
+  uint32_t *visits, *visits_rescan;
+  const ScanMode &mode;
+};
+
+Chunks view(const Chunks &g, const Half &h) {
+  Chunks v = g;
+  v.c0 = h.c0;
+  v.nch = h.c1;
+  return v;
+}
+
+// waves per block of the wave-per-tile / wave-per-window kernels (A/B: 2 of 1-4)
+constexpr int kWpb = 2;
+
+// Approximate max-plus scan of (sum, clean exit) over the runs of h: three
+// parallel kernels (the one-wave-per-run k_approx_scan when h has no tile).
+ks_status ascan(const ScanCall &c, const Work &w, const P1 &o, double *out, const Half &h, hipStream_t strm) {
+  const int64_t nruns = c.runs.n;
+  if (h.r1 <= h.r0) return KS_OK;
+  const dim3 gr((unsigned)(h.r1 - h.r0));
+  if (h.t1 <= h.t0) return launch(k_approx_scan, gr, dim3(64), 0, strm, c.lay.cbase, h.r1, o, out, h.r0);
+  const dim3 g4((unsigned)((h.t1 - h.t0 + kWpb - 1) / kWpb)), b4(64 * kWpb);  // a wave per tile, kWpb per block
+  KS_TRY(launch(k_ascan_tiles, g4, b4, 0, strm, c.lay.tbase, c.lay.cbase, nruns, w.trun, o, w.tagg, h.t0, h.t1));
+  KS_TRY(launch(k_ascan_runs, gr, dim3(64), 0, strm, c.lay.tbase, h.r1, w.tagg, w.tin, h.r0));
+  return launch(k_ascan_apply, g4, b4, 0, strm, c.lay.tbase, c.lay.cbase, nruns, w.trun, o, w.tin, out, h.t0, h.t1);
+}
+
+// P0: the predicted entries (Work::xh) of the chunks of h.
+ks_status predict(const ScanCall &c, const Work &w, const Half &h, hipStream_t strm) {
+  P1 pp = w.p1;
+  pp.asum = w.pa;
+  pp.cexit = w.pb;
+  pp.special = w.pz;
+  KS_HIP(hipMemsetAsync(w.pz + h.c0, 0, (size_t)(h.c1 - h.c0), strm));
+  const size_t lds = (size_t)2 << (2 * c.tv.approx_k);  // the fp16 prefix table
+  const int per_cu = lds <= ((size_t)32 << 10) ? 4 : 1;
+  const unsigned gl = (unsigned)std::max<int64_t>(
+      1, std::min<int64_t>((h.c1 - h.c0 + 1023) / 1024, (int64_t)c.ctx->num_cus * per_cu));
+  // every fourth index sampled, weighted 4 (at four 32-KiB blocks per CU:
+  // metric step 14.48 vs 14.62 ms median with every second, predictor 0.56 vs
+  // 0.64 ms; every eighth: predictor 0.21 ms but more mispredicted binades,
+  // carry + stitch 1.18 vs 0.85 ms; profiles/r4/ab4/ab_pred_log2.txt).
+  KS_HIP(hipFuncSetAttribute((const void *)k_predict<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KS_TRY(launch(k_predict<4>, dim3(gl), dim3(1024), lds, strm, view(w.g, h), c.total, c.k, c.tv.approx,
+                c.tv.approx_k, pp.asum, pp.cexit));
+  return ascan(c, w, pp, w.xh, h, strm);
+}
+
+// Pass 1 of the chunks of h on strm, appending to cand (every family but Plain).
+ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, const Half &h, hipStream_t strm,
+                     const Cand &cand) {
+  const Chunks gv = view(w.g, h);
+  const int64_t n = h.c1 - h.c0;
+  const TableView &tv = c.tv;
+  const EmitCfg &ec = c.ec;
+  const P1 &p1 = w.p1;
+  const SummP1 &sp1 = w.sp1;
+  const double *xh = plan.p1summ ? w.xh : nullptr;
+  const bool trlr = ec.trlr != 0;
+  auto blocks = [&](int64_t per) { return dim3((unsigned)((n + per - 1) / per)); };
+  auto persistent = [&](int per_cu) {
+    return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 1023) / 1024, (int64_t)per_cu * c.ctx->num_cus)));
+  };
+  switch (plan.family) {
+    case P1Family::Lds:
+      if (trlr)
+        return launch(k_pass1_lds<true>, persistent(1), dim3(1024), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1,
+                      cand, xh, sp1);
+      // integer small-k tables: the int32 pass, two blocks per CU (4.72 vs 5.57 ms
+      // at k = 7, profiles/r4/ab3/ab_k7pm1_int.txt; KS_NO_EXACT: the FP64 pass)
+      if (plan.exact)
+        return launch(k_pass1_lds_int, persistent(2), dim3(1024), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1,
+                      cand);
+      return launch(k_pass1_lds<false>, persistent(1), dim3(1024), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1,
+                    cand, xh, sp1);
+    case P1Family::Line: {
+      const int own = tv.line_own;
+      if (tv.rline && !trlr && !plan.p1summ && own == 3)  // weighted-rank code lines (k = 13)
+        return launch(k_pass1r<3>, blocks(kRankBlock), dim3(kRankBlock), 0, strm, gv, c.total, c.k, tv, ec, c.visits,
+                      p1, cand);
+      if (tv.line_kind == 3)  // wide lines: own 1..4 at k = 15..12 (J = 4..7)
+        return pick_int<1, 3, 4>(own, [&](auto o) {
+          return pick_bool(trlr, [&](auto t) {
+            return launch(k_pass1w<decltype(o)::value, decltype(t)::value>, blocks(kWideBlock), dim3(kWideBlock), 0,
+                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+          });
+        });
+      if (!plan.comp)
+        return pick_int<3, 4, 2>(own, [&](auto o) {
+          return pick_bool(trlr, [&](auto t) {
+            return launch(k_pass1l<decltype(o)::value, true, false, decltype(t)::value>, blocks(1024), dim3(1024), 0,
+                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+          });
+        });
+      return pick_int<3, 5, 2>(own, [&](auto o) {
+        return pick_bool(tv.nlut <= kLineLutMax, [&](auto l) {
+          return pick_bool(trlr, [&](auto t) {
+            return launch(k_pass1l<decltype(o)::value, false, decltype(l)::value, decltype(t)::value>, blocks(768),
+                          dim3(768), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+          });
+        });
+      });
     }
-    const unsigned g4 = (unsigned)((t1 - t0 + wpb - 1) / wpb);  // a wave per tile, wpb per block
-    hipLaunchKernelGGL(k_ascan_tiles, dim3(g4), dim3(64 * wpb), 0, strm, d_tbase, d_cbase, nruns, d_trun, o, d_tagg, t0,
-                       t1);
-    hipLaunchKernelGGL(k_ascan_runs, dim3((unsigned)(r1 - r0)), dim3(64), 0, strm, d_tbase, r1, d_tagg, d_tin, r0);
-    hipLaunchKernelGGL(k_ascan_apply, dim3(g4), dim3(64 * wpb), 0, strm, d_tbase, d_cbase, nruns, d_trun, o, d_tin, out,
-                       t0, t1);
-    KS_HIP(hipGetLastError());
+    case P1Family::F64Expanded:
+      // 512-lane blocks: up to 256 VGPRs, 152 used, no spills, 3 waves per SIMD
+      // (1024-lane blocks capped it at 128 with 17-29 VGPRs spilled to scratch:
+      // weighted rank k = 15 in-process 55.3 vs 61.4 ms, profiles/r5/ab/ab_p1pf_block.txt)
+      return pick_int<3, 4, 2>(plan.J, [&](auto j) {
+        return pick_bool(trlr, [&](auto t) {
+          return launch(k_pass1pf<decltype(j)::value, decltype(t)::value, 512>, blocks(512), dim3(512), 0, strm, gv,
+                        c.s->seq, c.total, c.k, tv, ec, c.visits, p1, cand, c.runs.packed, xh, sp1);
+        });
+      });
+    case P1Family::CompExpanded:
+      return pick_int<3, 5, 2>(plan.J, [&](auto j) {
+        return pick_bool(plan.lds_lut, [&](auto l) {
+          return pick_bool(trlr, [&](auto t) {
+            return launch(k_pass1p<decltype(j)::value, decltype(l)::value, decltype(t)::value>, blocks(kP1Block),
+                          dim3(kP1Block), 0, strm, gv, c.s->seq, c.total, c.k, tv, ec, c.visits, p1, cand,
+                          c.runs.packed, xh, sp1);
+          });
+        });
+      });
+    case P1Family::Plain:
+      break;
+  }
+  return fail(KS_ERR_INTERNAL, "chunked scan: no pass-1 launch per half for this table form");
+}
+
+// The tail chunks [plan.ctail, nch) of the expanded families (a latency-bound
+// serial walk each; no code store on these paths).
+ks_status pass1_tail(const ScanCall &c, const ScanPlan &plan, const Work &w, hipStream_t strm, const Cand &cand) {
+  const dim3 grid((unsigned)((w.g.nch - plan.ctail + 1023) / 1024));
+  auto go = [&](auto j, auto comp, auto l) {
+    return launch(k_pass1<decltype(j)::value, decltype(comp)::value, decltype(l)::value>, grid, dim3(1024), 0, strm,
+                  w.g, c.s->seq, c.total, c.k, c.tv, nullptr, c.ec, c.visits, w.p1, cand, plan.ctail, 1);
+  };
+  if (plan.family == P1Family::F64Expanded)
+    return pick_int<3, 4, 2>(plan.J, [&](auto j) { return go(j, std::false_type{}, std::false_type{}); });
+  if (plan.J == 5) return go(std::integral_constant<int, 5>{}, std::true_type{}, std::false_type{});
+  return pick_int<3, 4, 2>(plan.J, [&](auto j) {
+    return pick_bool(plan.lds_lut, [&](auto l) { return go(j, std::true_type{}, l); });
+  });
+}
+
+// P2-P5 (without the candidates) of half hi on stream strm, with its own
+// replay counter, error bits and fix list; kEvP2End / kEvP34End mark the
+// last half's phases.
+ks_status post_half(const ScanCall &c, const ScanPlan &plan, const Work &w, int hi, hipStream_t strm) {
+  const Half &h = plan.half[hi];
+  const bool last = hi == plan.nhalf - 1;
+  const Chunks gv = view(w.g, h);
+  const Chunks &g = w.g;
+  const TableView &tv = c.tv;
+  const P1 &p1 = w.p1;
+  const Summ &sm = w.sm;
+  const Carry &cr = w.cr;
+  const TileComp &tch = w.tcomp;
+  const ReplayBuf &rpb = w.rpb;
+  const uint8_t *seq = c.s->seq;
+  const int64_t total = c.total, nruns = c.runs.n;
+  const int k = c.k;
+  const int64_t nh = h.c1 - h.c0, nr = h.r1 - h.r0, nt = h.t1 - h.t0;
+  if (nh <= 0) return KS_OK;
+  unsigned long long *rep_h = w.cnts + 2 * kSegs + 2 * hi;
+  unsigned int *err_h = reinterpret_cast<unsigned int *>(rep_h + 1);
+  const dim3 gch_h((unsigned)((nh + 255) / 256)), gsum_h((unsigned)((nh + 1023) / 1024));
+  const dim3 bw(64 * kWpb);
+  // ---- P2 prediction, segment starts, summaries
+  KS_TRY(ascan(c, w, p1, w.xt, h, strm));
+  const int64_t wl = (h.c0 > 0 ? h.c0 - 1 : 0) / 64;
+  const int64_t nwm = (h.c1 + 63) / 64 - wl;
+  if (plan.exact) {  // the prescan is the carry (k_carry_exact)
+    KS_TRY(launch(k_carry_exact, gch_h, dim3(256), 0, strm, gv, p1, w.xt, cr));
+  } else if (plan.p1summ) {
+    // segment marks and summary selection in one pass over the chunks
+    KS_HIP(hipMemsetAsync(w.nfix + hi, 0, 8, strm));
+    KS_HIP(hipMemsetAsync(rpb.count + hi, 0, 8, strm));
+    KS_TRY(launch(k_marks_select, dim3((unsigned)((nwm + 3) / 4)), dim3(256), 0, strm, gv, p1, w.xt, w.flag, nwm,
+                  w.sp1, sm, w.fix + h.c0, w.nfix + hi, w.xh,
+                  w.dbg ? reinterpret_cast<unsigned long long *>(w.dbg + w.nwin * 9) : nullptr, rpb, hi));
+    // summaries of the listed chunks, a wave each; the LUT read through L2,
+    // not staged in LDS: a 54 KB LDS copy per block (2048 blocks, most
+    // without a listed chunk) cost more than the ~4 M lookups of the ~16 K
+    // listed chunks
+    const unsigned gw = (unsigned)std::max<int64_t>(1, (int64_t)c.ctx->num_cus * 8);
+    KS_TRY(launch(k_summ_fixw<false>, dim3(gw), dim3(256), 0, strm, g, seq, total, k, tv, w.xt, w.fix + h.c0,
+                  w.nfix + hi, sm, rpb, hi));
+  } else {
+    KS_TRY(launch(k_seg_marks, dim3((unsigned)((nwm + kWpb - 1) / kWpb)), bw, 0, strm, gv, p1, w.xt, w.flag, nwm));
+    if (plan.no_summ) {
+      KS_TRY(launch(k_summ_none, gsum_h, dim3(1024), 0, strm, gv, sm));
+    } else if (plan.lds_table) {
+      // small k: the table staged in LDS as for k_pass1_lds (from HBM / L2: 12.8 / 18.7 vs 3.8 / 6.4 ms)
+      if (plan.comp && plan.lds_lut) {
+        const size_t tb = (size_t)2 << (2 * k);
+        KS_HIP(hipFuncSetAttribute((const void *)k_summaries<true, true, true>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
+        KS_TRY(launch(k_summaries<true, true, true>, gsum_h, dim3(1024), tb, strm, gv, seq, total, k, tv, nullptr, p1,
+                      w.xt, sm));
+      } else {
+        const size_t tb = (size_t)8 << (2 * k);
+        KS_HIP(hipFuncSetAttribute((const void *)k_summaries<false, false, true>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
+        KS_TRY(launch(k_summaries<false, false, true>, gsum_h, dim3(1024), tb, strm, gv, seq, total, k, tv, nullptr,
+                      p1, w.xt, sm));
+      }
+    } else if (plan.lds_lut) {
+      KS_TRY(launch(k_summaries<true, true>, gsum_h, dim3(1024), 0, strm, gv, seq, total, k, tv, w.codes, p1, w.xt,
+                    sm));
+    } else if (plan.comp) {
+      KS_TRY(launch(k_summaries<true, false>, gsum_h, dim3(1024), 0, strm, gv, seq, total, k, tv, w.codes, p1, w.xt,
+                    sm));
+    } else {
+      KS_TRY(launch(k_summaries<false, false>, gsum_h, dim3(1024), 0, strm, gv, seq, total, k, tv, w.codes, p1, w.xt,
+                    sm));
+    }
+  }
+  if (last) KS_HIP(hipEventRecord(c.ctx->ev[kEvP2End], strm));
+
+  // ---- P3 carry by segments + P4 heads; then the gated per-run fallback
+  const int64_t wc = h.c0 / 64;
+  const unsigned nwc = (unsigned)((h.c1 - 1) / 64 - wc + 1);
+  const dim3 gtc((unsigned)(((h.c1 - 1) / 64 - wc + 1 + 3) / 4));  // 4 tiles per block
+  // FP64 tables: the R chunks' heads packed densely (k_heads_dense; lane per
+  // chunk, k_heads, measured slower at config 3: 29.9 vs 29.2 ms,
+  // profiles/r5/ab/ab_heads_dense_lane_pf_*.txt); compressed tables: k_heads
+  auto heads = [&](int gated) -> ks_status {
+    // (gated: a small grid-stride grid; it exits at once unless the carry fell back)
+    const unsigned full = plan.comp ? gch_h.x : (unsigned)((nh + 4 * kHeadSpan - 1) / (4 * kHeadSpan));
+    const dim3 gh(gated ? std::min<unsigned>(full, (unsigned)c.ctx->num_cus * 2) : full);
+    if (plan.comp)
+      return launch(k_heads<1, true>, gh, dim3(256), 0, strm, gv, seq, total, k, tv, w.codes, cr, err_h, gated);
+    if (plan.J == 4 && tv.line)
+      return launch(k_heads_dense<4, false, true>, gh, dim3(256), 0, strm, gv, seq, total, k, tv, w.codes, cr, err_h,
+                    gated);
+    return pick_int<2, 4, 1>(plan.J, [&](auto j) {
+      return launch(k_heads_dense<decltype(j)::value, false, false>, gh, dim3(256), 0, strm, gv, seq, total, k, tv,
+                    w.codes, cr, err_h, gated);
+    });
+  };
+  if (plan.exact) {
+    KS_TRY(heads(0));
+  } else {
+    const dim3 gcw((nwc + kWpb - 1) / kWpb);
+    KS_TRY(launch(k_tile_comp, gtc, dim3(256), 0, strm, gv, sm, tch));
+    KS_TRY(pick_bool(plan.comp, [&](auto cp) {
+      return launch(k_carry_win<decltype(cp)::value>, gcw, bw, 0, strm, gv, w.flag, seq, total, k, tv, w.codes, p1, sm,
+                    cr, tch, rpb, rep_h, err_h, w.dbg);
+    }));
+    KS_TRY(launch(k_tile_apply, gtc, dim3(256), 0, strm, gv, sm, tch, cr, err_h, 0));
+    KS_TRY(heads(0));
+    KS_TRY(launch(k_fallback_prep, dim3(1), dim3(1), 0, strm, err_h, rep_h, plan.force_fb));
+    if (nr > 0) {
+      KS_TRY(pick_bool(plan.comp, [&](auto cp) {
+        return launch(k_carry_run<decltype(cp)::value>, dim3((unsigned)nr), dim3(64), 0, strm, gv, c.lay.cbase, h.r1,
+                      seq, total, k, tv, w.codes, p1, sm, cr, tch, rpb, rep_h, err_h, nullptr, h.r0);
+      }));
+      KS_TRY(launch(k_tile_apply, gtc, dim3(256), 0, strm, gv, sm, tch, cr, err_h, 1));
+    }
+    KS_TRY(heads(1));
+  }
+  if (last) KS_HIP(hipEventRecord(c.ctx->ev[kEvP34End], strm));
+
+  // ---- P5 stitch
+  const dim3 gst((unsigned)((nt + kWpb - 1) / kWpb));
+  if (nt > 0)
+    KS_TRY(launch(k_stitch_tiles, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, p1, cr, w.xagg, h.t0,
+                  h.t1));
+  if (nr > 0)
+    KS_TRY(launch(k_stitch_runs, dim3((unsigned)nr), dim3(64), 0, strm, c.lay.tbase, h.r1, c.runs.a, c.runs.b,
+                  c.runs.seq, c.ec, w.xagg, w.xtin, c.rb, w.rss[hi], h.r0));
+  if (nt > 0)
+    KS_TRY(launch(k_stitch_emit, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, c.runs.a, c.runs.seq,
+                  p1, cr, c.ec, w.xtin, c.rb, w.rss[hi], err_h, h.t0, h.t1));
+  return KS_OK;
+}
+
+// Candidates (count read on the device) and rescans of half h's lists on rst
+// (the rescan slots in list order: sorted longest first they took 5.23 vs
+// 3.56 ms at config 3, profiles/r4/ab2/ab_rank.txt).
+ks_status emit_rescan(const ScanCall &c, const ScanPlan &plan, const Work &w, int h, hipStream_t rst) {
+  const Rescan &rs = w.rss[h];
+  KS_TRY(launch(k_candidates, dim3((unsigned)((w.cands[h].cap + 255) / 256)), dim3(256), 0, rst, w.g, c.runs.a,
+                c.lay.cbase, c.runs.n, c.runs.seq, c.ec, w.cands[h], w.cr, c.rb, rs));
+  if (h == plan.nhalf - 1) KS_HIP(hipEventRecord(c.ctx->ev[kEvCandEnd], rst));
+  return launch_scan_lane(c.ctx, c.s->seq, c.total, rs.a, rs.b, rs.seq, rs.cap, c.k, c.tv, c.ec.mw, c.ec.min_score,
+                          c.visits_rescan, c.rb, rs.count, rs.segcap, c.mode, 0, nullptr, c.runs.packed, rst);
+}
+
+// Diagnostics (at the end of the file), called under their flags.
+void debug_verify(const ScanCall &c, const Work &w);
+ks_status debug_carry_report(const ScanPlan &plan, Work &w, int64_t nruns);
+ks_status debug_rescan_hist(const Rescan &rs, const unsigned long long *counts, int k, int64_t nres);
+
+}  // namespace
+
+ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, const RunLayout &lay, int k,
+                       const TableView &tv, uint64_t mw, double min_score, uint32_t *visits,
+                       uint32_t *visits_rescan, const RegionBuf &rb, ks_scan_stats *stats, const ScanMode &mode) {
+  hipStream_t st = ctx->stream, side = ctx->side, hi = ctx->hi;
+  const int64_t nruns = runs.n, nch = lay.nch, ntiles = lay.ntiles;
+  ctx->chunked_events = false;
+  if (nruns == 0 || nch == 0) return KS_OK;
+  const EmitCfg ec{mode.trlr, mw, min_score, mode.min_len, mode.ks, k};
+  const ScanCall c{ctx, s, s->offsets_host[s->nseq], k, tv, ec, runs, lay, rb, visits, visits_rescan, mode};
+  const ScanPlan plan = plan_scan(tv, k, mode, runs, lay);
+  auto record = [&](int e, hipStream_t strm) -> ks_status {
+    KS_HIP(hipEventRecord(ctx->ev[e], strm));
     return KS_OK;
   };
-  double *d_xh = reinterpret_cast<double *>(W + o_xh);
-  long long *spd = reinterpret_cast<long long *>(W + o_spd);
-  const SummP1 sp1{reinterpret_cast<int32_t *>(W + o_spe), spd, spd + 2 * nch, spd + 4 * nch,
-                   reinterpret_cast<int32_t *>(W + o_spa)};
-  unsigned long long *d_nfix = reinterpret_cast<unsigned long long *>(W + o_fix);  // [2]: one per half
-  int64_t *d_fix = reinterpret_cast<int64_t *>(W + o_fix + 16);
-  // cnts: [0, kSegs) candidate counters, [kSegs, 2 kSegs) rescan counters,
-  // [2 kSegs + 2h] replays, [2 kSegs + 2h + 1] error bits (u32) of half h,
-  // [2 kSegs + 8, 3 kSegs + 8) the region counters' copy, [3 kSegs + 8,
-  // 5 kSegs + 8) the second half's candidate and rescan counters
+  auto wait = [&](hipStream_t strm, int e) -> ks_status {
+    KS_HIP(hipStreamWaitEvent(strm, ctx->ev[e], 0));
+    return KS_OK;
+  };
+
+  // ---- workspace
+  size_t bytes = 0;
+  carve(nullptr, plan, nch, ntiles, runs.packed, &bytes);
+  void *wsp = nullptr;
+  KS_TRY(ensure(ctx, SLOT_CHUNK_A, bytes, &wsp));
+  Work w = carve(static_cast<char *>(wsp), plan, nch, ntiles, runs.packed, &bytes);
+  w.p1.epoch = ++ctx->scan_epoch;
+  unsigned long long *cnts = w.cnts;
   KS_HIP(hipMemsetAsync(cnts, 0, 8 * (2 * kSegs + 8), st));
   KS_HIP(hipMemsetAsync(cnts + 3 * kSegs + 8, 0, 8 * (2 * kSegs), st));
-  unsigned long long *d_replays = cnts + 2 * kSegs;
-
-  // Candidates and rescans in one list per half: the first half's are
-  // emitted and rescanned while the second half is post-processed (a list
-  // cannot be read while the other half's pass 1 still appends to it).
-  int64_t ccap = std::max<int64_t>(1 << 16, nch / 4);  // per list
+  if (plan.need_codes) {
+    void *cp = nullptr;
+    const int64_t ctiles = (nch + 63) / 64;  // code store tiles (global chunk index / 64): 2 B x 256 per chunk
+    KS_TRY(ensure(ctx, SLOT_CHUNK_B, (size_t)ctiles * 64 * CH * 2, &cp));
+    w.codes = static_cast<uint16_t *>(cp);
+  }
+  int64_t ccap = std::max<int64_t>(1 << 16, nch / 4);  // per candidate list
   const size_t cand_bytes = ctx->slots[SLOT_CHUNK_C].bytes;  // use what the grow-only slot holds
   if (cand_bytes > 2048 && (cand_bytes - 2048) / 80 > (size_t)ccap) ccap = (int64_t)((cand_bytes - 2048) / 80);
   const int64_t csegcap = ccap / kSegs;
   ccap = csegcap * kSegs;
   void *cbuf = nullptr;
   KS_TRY(ensure(ctx, SLOT_CHUNK_C, (size_t)ccap * 80 + 2048, &cbuf));
-  auto cand_list = [&](int h) {
-    long long *b = reinterpret_cast<long long *>(cbuf) + (size_t)h * 5 * ccap;
-    return Cand{b, b + ccap, b + 2 * ccap, reinterpret_cast<double *>(b + 3 * ccap),
-                h ? cnts + 3 * kSegs + 8 : cnts, ccap, csegcap};
-  };
-  const Cand cands[2] = {cand_list(0), cand_list(1)};
-  Cand cand = cands[0];  // (the list the pass-1 launches below append to: the second half's switches it)
   // kmer_regions: a rescan accompanies a region in the same segment; tr_lr
   // rescans every closed excursion, so its capacity grows on its own
   const int64_t rsegcap = std::max<int64_t>(rb.segcap, ctx->rescan_segcap);
-  const int64_t rcap = rsegcap * kSegs;  // per list
+  const int64_t rcap = rsegcap * kSegs;  // per rescan list
   void *rsb = nullptr;
   KS_TRY(ensure(ctx, SLOT_WORK_A, (size_t)rcap * 40 + 2048, &rsb));
-  auto rescan_list = [&](int h) {
+  for (int h = 0; h < 2; ++h) {
+    long long *cb = reinterpret_cast<long long *>(cbuf) + (size_t)h * 5 * ccap;
+    w.cands[h] = Cand{cb, cb + ccap, cb + 2 * ccap, reinterpret_cast<double *>(cb + 3 * ccap),
+                      h ? cnts + 3 * kSegs + 8 : cnts, ccap, csegcap};
     int64_t *b = reinterpret_cast<int64_t *>(static_cast<char *>(rsb) + (size_t)h * ((size_t)rcap * 20 + 256));
-    return Rescan{b, b + rcap, reinterpret_cast<int32_t *>(b + 2 * rcap), h ? cnts + 4 * kSegs + 8 : cnts + kSegs,
-                  rcap, rsegcap};
-  };
-  const Rescan rss[2] = {rescan_list(0), rescan_list(1)};
-  const Rescan &rs = rss[0];
-  // KS_DEBUG_CARRY=1: per-window carry statistics to stderr (diagnostics only)
-  static const bool dbg_on = getenv("KS_DEBUG_CARRY") != nullptr;
-  long long *dbg = nullptr;
-  if (dbg_on) {
-    KS_HIP(hipMalloc(&dbg, (nwin * 9 + 4) * sizeof(long long)));
-    KS_HIP(hipMemsetAsync(dbg, 0, (nwin * 9 + 4) * sizeof(long long), st));
+    w.rss[h] = Rescan{b, b + rcap, reinterpret_cast<int32_t *>(b + 2 * rcap), h ? cnts + 4 * kSegs + 8 : cnts + kSegs,
+                      rcap, rsegcap};
+  }
+  if (plan.debug_carry) {  // per-window carry statistics to stderr
+    KS_HIP(hipMalloc(&w.dbg, (w.nwin * 9 + 4) * sizeof(long long)));
+    KS_HIP(hipMemsetAsync(w.dbg, 0, (w.nwin * 9 + 4) * sizeof(long long), st));
   }
 
-  // ---- P0 chunks, P1 gather pass
-  KS_HIP(hipEventRecord(ctx->ev[7], st));
-  if (nruns > 0) {
-    hipLaunchKernelGGL(k_tile_runs, dim3((unsigned)nruns), dim3(256), 0, st, d_tbase, nruns, d_trun_map);
-    KS_HIP(hipGetLastError());
-  }
+  // ---- P0 chunk layout, predictor
+  KS_TRY(record(kEvBegin, st));
+  KS_TRY(launch(k_tile_runs, dim3((unsigned)nruns), dim3(256), 0, st, lay.tbase, nruns, w.trun));
   if (ntiles > 0)
-    hipLaunchKernelGGL(k_make_chunks, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, runs.a, d_cbase, d_tbase,
-                       d_trun_map, ntiles, k, runs.b, mode.trlr, g);
-  KS_HIP(hipGetLastError());
-  const unsigned gch = (unsigned)((nch + 255) / 256);
-  const unsigned gch1k = (unsigned)((nch + 1023) / 1024);
-  const int Jt = (tv.ext != nullptr) ? tv.ext_J : 1;
-  const bool lds_table = k <= kLdsTableK && runs.packed != nullptr && getenv("KS_NO_LDS_TABLE") == nullptr;
-  // pass-1 summaries (no per-position code store): compressed expanded
-  // tables on the pipelined pass with a binade predictor (a table without
-  // one, a failed allocation of the predictor, is scanned unexpanded)
-  const bool line = tv.line != nullptr && !lds_table && runs.packed != nullptr;  // line table: k_pass1l
-  // (FP64 tables: no summaries by default -- see no_summ below; at k = 15
-  // 50.6 vs 53.7 ms with k_pass1pf's pass-1 summaries and 59.4 with
-  // k_summaries, at k = 13 29.8 vs 30.2 with k_summaries,
-  // profiles/r5/ab/ab_nosumm_*.txt.  KS_F64_P1SUMM=1: pass-1 summaries (FP64
-  // lines, expanded J 2..4, k_pass1pf); KS_F64_P1SUMM=0: k_summaries)
-  const char *f64e = getenv("KS_F64_P1SUMM");
-  const bool f64_summ = !comp && !lds_table && f64e && atoi(f64e) != 0 && (line || (Jt >= 2 && Jt <= 4));
-  // (small k, the table in LDS: pass-1 summaries from the LDS-staged table;
-  // the k_summaries path after the prescan took 13.3 vs 8.8 ms at k = 7 log2)
-  const bool lds_summ = lds_table;
-  // integer tables: the exact carry (k_carry_exact) needs no predictor and
-  // no summaries (KS_NO_EXACT: the general path, for A/B runs and tests)
-  // (on the table forms of the pipelined passes -- LDS, line, expanded; an
-  // unexpanded table of another size takes the code-store pass and k_summaries)
-  // (exact while every partial sum of a run is: |s| <= 2^20 over fewer than
-  // 2^32 indices stays below 2^52; KS_TEST_SEG_FALLBACK, which forces the
-  // general carry's per-run fallback, takes the general path)
-  const int force_fb = getenv("KS_TEST_SEG_FALLBACK") != nullptr ? 1 : 0;  // tests: force the fallback path
-  const bool exact = tv.exact && !mode.trlr && runs.packed != nullptr && (lds_table || line || Jt >= 2) &&
-                     lay.longest < ((int64_t)1 << 32) && !force_fb && getenv("KS_NO_EXACT") == nullptr;
-  // FP64 tables without KS_F64_P1SUMM: no chunk summaries at all (a summary
-  // serves a chunk only while its carry-in stays >= 64 in one binade; weighted
-  // rank values in [-0.5, 0.5] keep the carry far below that: 5,598 of 11.96 M
-  // chunks at config 3 were summary-served, 1.0 M replayed)
-  const bool no_summ = getenv("KS_NO_SUMMARIES") != nullptr || (!comp && !lds_table && !f64e);
-  const bool p1summ = !exact && (lds_table ? lds_summ : (comp ? (Jt >= 2 || line) : f64_summ)) &&
-                      runs.packed != nullptr && tv.approx != nullptr;
-  // (the carry reads no replay slots unless k_marks_select wrote them)
-  if (!p1summ) rpb.slot = nullptr;
-  // pass-1 summaries are read where pass 1 wrote them (summ_at): the selection
-  // writes a byte per chunk instead of copying 56 (metric step 14.47 vs 14.61 ms
-  // median in-process, profiles/r4/ab4/ab_copy_log2.txt)
-  if (p1summ) {
-    sm.sel = reinterpret_cast<uint8_t *>(W + o_ssel);
-    sm.pD = sp1.D;
-    sm.pM = sp1.M;
-    sm.pN = sp1.N;
-    sm.pA = sp1.A;
-  }
-  // per-index code store (uint16 per scan index, 2 B x 256 per chunk):
-  // written by the compressed unexpanded pass 1 (k_pass1<1, ...>) for the
-  // binade summaries (k_summaries)
-  uint16_t *codes = nullptr;
-  if (comp && !p1summ && !exact && !lds_table) {
-    void *cp = nullptr;
-    const int64_t ctiles = (nch + 63) / 64;  // code store tiles (global chunk index / 64)
-    KS_TRY(ensure(ctx, SLOT_CHUNK_B, (size_t)ctiles * 64 * CH * 2, &cp));
-    codes = static_cast<uint16_t *>(cp);
-  }
-  // Two halves of the runs (pass-1-summary path): the second half's pass 1
-  // (side stream) runs while the first half's latency-bound later passes
-  // (carry, stitch) run on the main stream; halves split at a run boundary,
-  // so no carry or stitch crosses it.
-  struct Half {
-    int64_t c0, c1, r0, r1, t0, t1;
-  };
-  const int64_t ctail_all = nch > 1024 ? nch - 1024 : 0;
-  // FP64 line tables (weighted rank) without pass-1 summaries: one part.
-  // Their two pass-1 launches ran side by side and ended together (15.2 ms
-  // each, profiles/r5/rank/step_timeline_rank_k13_twopart.txt), so the first part's
-  // post-processing never ran under the second's pass 1: 27.75 vs 28.56 ms
-  // in one part (profiles/r5/ab/ab_nosplit_k13.txt).  (Round 3, with
-  // k_summaries after pass 1: two parts 31.5 vs 32.7, profiles/r3/rank/.)
-  // (the exact carry's post-processing is short: one part -- two measured the
-  // same at lower run-to-run spread, 6.44 vs 6.55 ms median at k = 7,
-  // profiles/r4/ab3/ab_k7pm1_exact_split.txt)
-  // (below ~2 M chunks, ~500 Mbp, one part: at the 8-way shard, 1.5 M chunks,
-  // 2.38 vs 2.42 ms in-process; 4-way, 3 M chunks, two parts 4.24 vs 4.37;
-  // profiles/r5/ab/ab_one_part_*.txt.  KS_SPLIT_MIN_CHUNKS: the threshold --
-  // tests set 0 to run the two-part path on small genomes)
-  const char *smin = getenv("KS_SPLIT_MIN_CHUNKS");
-  const int64_t split_min = smin ? atoll(smin) : ((int64_t)2 << 20);
-  // (FP64 expanded tables without summaries stay in one part: two measured
-  // 52.1 vs 51.6 ms at k = 15, 46.0 vs 44.8 at k = 14,
-  // profiles/r5/ab/ab_nosumm_split_k15.txt, ab_nosumm_k14.txt)
-  const bool split = p1summ &&
-                     nch > split_min && lay.split_r > 0 && lay.split_r < nruns &&
-                     lay.split_c >= 1024 && lay.split_c + 1024 <= ctail_all;
-  Half halves[2];
-  int nhalf = 1;
-  halves[0] = Half{0, nch, 0, nruns, 0, ntiles};
-  if (split) {
-    nhalf = 2;
-    halves[0] = Half{0, lay.split_c, 0, lay.split_r, 0, lay.split_t};
-    halves[1] = Half{lay.split_c, nch, lay.split_r, nruns, lay.split_t, ntiles};
-  }
-  auto view = [&](const Half &h) {
-    Chunks v = g;
-    v.c0 = h.c0;
-    v.nch = h.c1;
-    return v;
-  };
-  bool side_forked = false;  // the side stream already waits for the chunks (P0 overlap)
-  if (p1summ) {  // P0: predicted entries of each half (the second half's on the side stream, under
-                 // the first half's predictor and pass 1)
-    P1 pp = p1;
-    pp.asum = reinterpret_cast<double *>(W + o_pa);
-    pp.cexit = reinterpret_cast<double *>(W + o_pb);
-    pp.special = reinterpret_cast<uint8_t *>(W + o_pz);
-    auto predict = [&](const Half &h, hipStream_t strm) -> ks_status {
-      KS_HIP(hipMemsetAsync(W + o_pz + h.c0, 0, (size_t)(h.c1 - h.c0), strm));
-      const size_t lds = (size_t)2 << (2 * tv.approx_k);  // the fp16 prefix table
-      const int per_cu = lds <= ((size_t)32 << 10) ? 4 : 1;
-      const unsigned gl = (unsigned)std::max<int64_t>(
-          1, std::min<int64_t>((h.c1 - h.c0 + 1023) / 1024, (int64_t)ctx->num_cus * per_cu));
-      // every fourth index sampled, weighted 4 (at four 32-KiB blocks per CU:
-      // metric step 14.48 vs 14.62 ms median with every second, predictor 0.56 vs
-      // 0.64 ms; every eighth: predictor 0.21 ms but more mispredicted binades,
-      // carry + stitch 1.18 vs 0.85 ms; profiles/r4/ab4/ab_pred_log2.txt).
-      KS_HIP(hipFuncSetAttribute((const void *)k_predict<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k_predict<4>, dim3(gl), dim3(1024), lds, strm, view(h), total, k, tv.approx, tv.approx_k,
-                         pp.asum, pp.cexit);
-      KS_HIP(hipGetLastError());
-      return ascan(pp, d_xh, h.r0, h.r1, h.t0, h.t1, strm);
-    };
+    KS_TRY(launch(k_make_chunks, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, runs.a, lay.cbase, lay.tbase,
+                  w.trun, ntiles, k, runs.b, mode.trlr, w.g));
+  bool side_forked = false;  // the side stream already waits for the chunks
+  if (plan.p1summ) {
     // the first half's predictor and prescan first (they gate its pass 1;
     // the predictor holds whole CUs: 128 KiB of LDS per block), then the
     // second half's on the side stream, under the first half's pass 1 (also
     // at shard sizes: both first on the main stream measured 2.48 vs 2.38 ms
     // at the 8-way shard, profiles/r4/ab/ab_shard8.txt)
-    KS_TRY(predict(halves[0], st));
-    if (split) {
+    KS_TRY(predict(c, w, plan.half[0], st));
+    if (plan.split) {
       side_forked = true;
-      KS_HIP(hipEventRecord(ctx->ev[16], st));
-      KS_HIP(hipStreamWaitEvent(ctx->side, ctx->ev[16], 0));
-      KS_TRY(predict(halves[1], ctx->side));
+      KS_TRY(record(kEvPredictFork, st));
+      KS_TRY(wait(side, kEvPredictFork));
+      KS_TRY(predict(c, w, plan.half[1], side));
     }
   }
-  KS_HIP(hipEventRecord(ctx->ev[8], st));
-  const bool lds_lut = comp && tv.nlut <= kLdsLutMax;
-#define KS_P1(J, C, L)                                                                                       \
-  hipLaunchKernelGGL((k_pass1<J, C, L>), dim3(J == 1 ? gch : gch1k), dim3(J == 1 ? 256 : 1024), 0, st, g, s->seq, \
-                     total, k, tv, codes, ec, visits, p1, cand, (int64_t)0, 0)
-  // k_pass1p leaves the chunks whose reads could pass the end of the buffer
-  // (chunk starts increase with the chunk index, so they are among the last
-  // kP1TailMargin + CH chunks) to k_pass1
-  const int64_t ctail = nch > 1024 ? nch - 1024 : 0;
-#define KS_P1T(J, L) KS_P1TC(J, true, L)
-#define KS_P1TC(J, C, L)                                                                                       \
-  hipLaunchKernelGGL((k_pass1<J, C, L>), dim3((unsigned)((nch - ctail + 1023) / 1024)), dim3(1024), 0, side, g, \
-                     s->seq, total, k, tv, p1summ ? nullptr : codes, ec, visits, p1, cand, ctail, 1)
-  // compressed tables are scanned expanded only on the summarising pass
-  const int J = (tv.ext != nullptr && (p1summ || exact || !comp)) ? tv.ext_J : 1;
-  const bool pipelined = runs.packed != nullptr;
-#define KS_P1P(J, L, GV, GRID, STRM)                                                                           \
-  do {                                                                                                       \
-    if (ec.trlr)                                                                                             \
-      hipLaunchKernelGGL((k_pass1p<J, L, true>), dim3(GRID), dim3(kP1Block), 0, STRM, GV, s->seq, total, k, tv, \
-                         ec, visits, p1, cand, runs.packed, p1summ ? d_xh : nullptr, sp1);                   \
-    else                                                                                                     \
-      hipLaunchKernelGGL((k_pass1p<J, L, false>), dim3(GRID), dim3(kP1Block), 0, STRM, GV, s->seq, total, k, tv, \
-                         ec, visits, p1, cand, runs.packed, p1summ ? d_xh : nullptr, sp1);                   \
-  } while (0)
-  if (lds_table) {
-    // small k: the whole table in LDS, persistent blocks (one per CU), no
-    // code store; with pass-1 summaries the halves as for line tables
-    // integer small-k tables: the int32 pass (4.72 vs 5.57 ms at k = 7,
-    // profiles/r4/ab3/ab_k7pm1_int.txt; KS_NO_EXACT: the FP64 pass)
-    const bool lds_int = true;
-    auto p1lds = [&](const Half &h, hipStream_t strm) {
-      const Chunks gv = view(h);
-      const unsigned gl = (unsigned)std::max<int64_t>(1, std::min<int64_t>((h.c1 - h.c0 + 1023) / 1024, ctx->num_cus));
-      const double *xh = p1summ ? d_xh : nullptr;
-      if (ec.trlr)
-        hipLaunchKernelGGL(k_pass1_lds<true>, dim3(gl), dim3(1024), 0, strm, gv, total, k, tv, ec, visits, p1, cand, xh,
-                           sp1);
-      else if (exact && lds_int)  // (two blocks per CU)
-        hipLaunchKernelGGL(k_pass1_lds_int, dim3((unsigned)std::max<int64_t>(
-                                                 1, std::min<int64_t>((h.c1 - h.c0 + 1023) / 1024, 2 * ctx->num_cus))),
-                           dim3(1024), 0, strm, gv, total, k, tv, ec, visits, p1, cand);
-      else if (exact)
-        hipLaunchKernelGGL((k_pass1_lds<false, true>), dim3(gl), dim3(1024), 0, strm, gv, total, k, tv, ec, visits, p1,
-                           cand, xh, sp1);
-      else
-        hipLaunchKernelGGL(k_pass1_lds<false>, dim3(gl), dim3(1024), 0, strm, gv, total, k, tv, ec, visits, p1, cand, xh,
-                           sp1);
-    };
-    if (split) {
-      KS_HIP(hipEventRecord(ctx->ev[17], st));
-      KS_HIP(hipStreamWaitEvent(ctx->hi, ctx->ev[17], 0));
-      if (!side_forked) KS_HIP(hipStreamWaitEvent(ctx->side, ctx->ev[17], 0));
-      p1lds(halves[0], ctx->hi);
-      KS_HIP(hipGetLastError());
-      KS_HIP(hipEventRecord(ctx->ev[12], ctx->hi));
-      KS_HIP(hipStreamWaitEvent(st, ctx->ev[12], 0));
-      cand = cands[1];
-      p1lds(halves[1], ctx->side);
-    } else {
-      p1lds(halves[0], st);
-    }
-    codes = nullptr;
-  } else if (line && (p1summ || exact || !comp)) {
-    // line tables: every chunk (no tail: a lane's bases come from guarded loads)
-    const bool lut = tv.nlut <= kLineLutMax;
-#define KS_P1L(O, F, L, GV, GRID, STRM)                                                                        \
-  do {                                                                                                       \
-    if (ec.trlr)                                                                                             \
-      hipLaunchKernelGGL((k_pass1l<O, F, L, true>), dim3(GRID), dim3(F ? 1024 : 768), 0, STRM, GV, total, k, tv, ec, \
-                         visits, p1, cand, p1summ ? d_xh : nullptr, sp1);                                    \
-    else                                                                                                     \
-      hipLaunchKernelGGL((k_pass1l<O, F, L, false>), dim3(GRID), dim3(F ? 1024 : 768), 0, STRM, GV, total, k, tv, \
-                         ec, visits, p1, cand, p1summ ? d_xh : nullptr, sp1);                                \
-  } while (0)
-    auto p1l = [&](const Half &h, hipStream_t strm) {
-      const Chunks gv = view(h);
-      const int own = tv.line_own;
-      if (tv.rline && !ec.trlr && !p1summ && own == 3) {  // weighted-rank code lines (k = 13)
-        hipLaunchKernelGGL(k_pass1r<3>, dim3((unsigned)((h.c1 - h.c0 + kRankBlock - 1) / kRankBlock)),
-                           dim3(kRankBlock), 0, strm, gv, total, k, tv, ec, visits, p1, cand);
-        return;
-      }
-      if (tv.line_kind == 3) {  // wide lines
-        const unsigned grid = (unsigned)((h.c1 - h.c0 + kWideBlock - 1) / kWideBlock);
-#define KS_P1W(O)                                                                                             \
-  do {                                                                                                      \
-    if (ec.trlr)                                                                                            \
-      hipLaunchKernelGGL((k_pass1w<O, true>), dim3(grid), dim3(kWideBlock), 0, strm, gv, total, k, tv, ec, visits, \
-                         p1, cand, p1summ ? d_xh : nullptr, sp1);                                           \
-    else                                                                                                    \
-      hipLaunchKernelGGL((k_pass1w<O, false>), dim3(grid), dim3(kWideBlock), 0, strm, gv, total, k, tv, ec, visits, \
-                         p1, cand, p1summ ? d_xh : nullptr, sp1);                                           \
-  } while (0)
-        if (own == 1) KS_P1W(1);  // k = 15 (J = 4)
-        else if (own == 2) KS_P1W(2);  // k = 14 (J = 5)
-        else if (own == 3) KS_P1W(3);  // k = 13 (J = 6)
-        else KS_P1W(4);  // k = 12 (J = 7)
-#undef KS_P1W
-        return;
-      }
-      const int bs = comp ? 768 : 1024;
-      const unsigned grid = (unsigned)((h.c1 - h.c0 + bs - 1) / bs);
-      if (!comp) {
-        if (own == 4) KS_P1L(4, true, false, gv, grid, strm);
-        else if (own == 3) KS_P1L(3, true, false, gv, grid, strm);
-        else KS_P1L(2, true, false, gv, grid, strm);
-      } else if (lut) {
-        if (own == 5) KS_P1L(5, false, true, gv, grid, strm);
-        else if (own == 4) KS_P1L(4, false, true, gv, grid, strm);
-        else if (own == 3) KS_P1L(3, false, true, gv, grid, strm);
-        else KS_P1L(2, false, true, gv, grid, strm);
-      } else {
-        if (own == 5) KS_P1L(5, false, false, gv, grid, strm);
-        else if (own == 4) KS_P1L(4, false, false, gv, grid, strm);
-        else if (own == 3) KS_P1L(3, false, false, gv, grid, strm);
-        else KS_P1L(2, false, false, gv, grid, strm);
-      }
-    };
-#undef KS_P1L
-    if (split) {  // the halves at once, as the expanded-table pass below
-      KS_HIP(hipEventRecord(ctx->ev[17], st));
-      KS_HIP(hipStreamWaitEvent(ctx->hi, ctx->ev[17], 0));
-      if (!side_forked) KS_HIP(hipStreamWaitEvent(ctx->side, ctx->ev[17], 0));
-      p1l(halves[0], ctx->hi);
-      KS_HIP(hipGetLastError());
-      KS_HIP(hipEventRecord(ctx->ev[12], ctx->hi));
-      KS_HIP(hipStreamWaitEvent(st, ctx->ev[12], 0));
-      cand = cands[1];
-      p1l(halves[1], ctx->side);
-    } else {
-      p1l(halves[0], st);
-    }
-    KS_HIP(hipGetLastError());
-  } else if (!comp && J >= 2 && J <= 4 && pipelined) {  // FP64 expanded table (weighted rank)
-    hipStream_t side = ctx->side;
-    const bool tail = nch > ctail;
-    const double *xh = p1summ ? d_xh : nullptr;
-#define KS_P1PF(J, GV, STRM, B)                                                                                \
-    do {                                                                                                       \
-      const unsigned grid_ = (unsigned)((h.c1 - h.c0 + (B) - 1) / (B));                                        \
-      if (ec.trlr) hipLaunchKernelGGL((k_pass1pf<J, true, B>), dim3(grid_), dim3(B), 0, STRM, GV, s->seq, total, k, \
-                                      tv, ec, visits, p1, cand, runs.packed, xh, sp1);                         \
-      else hipLaunchKernelGGL((k_pass1pf<J, false, B>), dim3(grid_), dim3(B), 0, STRM, GV, s->seq, total, k, tv, \
-                              ec, visits, p1, cand, runs.packed, xh, sp1);                                     \
-    } while (0)
-    // 512-lane blocks: up to 256 VGPRs, 152 used, no spills, 3 waves per SIMD
-    // (1024-lane blocks capped it at 128 with 17-29 VGPRs spilled to scratch:
-    // weighted rank k = 15 in-process 55.3 vs 61.4 ms, profiles/r5/ab/ab_p1pf_block.txt)
-    auto p1f = [&](const Half &h, hipStream_t strm) {
-      const Chunks gv = view(h);
-      if (J == 4) KS_P1PF(4, gv, strm, 512); else if (J == 3) KS_P1PF(3, gv, strm, 512); else KS_P1PF(2, gv, strm, 512);
-    };
-    if (tv.rline && !ec.trlr && !p1summ && !split && (k == 14 || k == 15)) {
-      // weighted-rank code lines (k = 14 / 15: J = 4 / 3 per 128-B line read
-      // against 3 / 2 per FP64 expanded entry); every chunk (guarded base loads)
-      const unsigned grid = (unsigned)((nch + kRankBlock - 1) / kRankBlock);
-      if (k == 15)
-        hipLaunchKernelGGL(k_pass1r<1>, dim3(grid), dim3(kRankBlock), 0, st, view(halves[0]), total, k, tv, ec, visits,
-                           p1, cand);
-      else
-        hipLaunchKernelGGL(k_pass1r<2>, dim3(grid), dim3(kRankBlock), 0, st, view(halves[0]), total, k, tv, ec, visits,
-                           p1, cand);
-      KS_HIP(hipGetLastError());
-    } else {
-#undef KS_P1PF
-    auto p1tail = [&]() {
-      if (J == 4) KS_P1TC(4, false, false); else if (J == 3) KS_P1TC(3, false, false); else KS_P1TC(2, false, false);
-    };
-    if (split) {  // the halves at once, as the compressed pass below
-      KS_HIP(hipEventRecord(ctx->ev[17], st));
-      KS_HIP(hipStreamWaitEvent(ctx->hi, ctx->ev[17], 0));
-      if (!side_forked) KS_HIP(hipStreamWaitEvent(side, ctx->ev[17], 0));
-      p1f(halves[0], ctx->hi);
-      KS_HIP(hipGetLastError());
-      KS_HIP(hipEventRecord(ctx->ev[12], ctx->hi));
-      KS_HIP(hipStreamWaitEvent(st, ctx->ev[12], 0));
-      cand = cands[1];  // (the tail chunks are the second half's)
-      if (tail) {
-        p1tail();
-        KS_HIP(hipGetLastError());
-      }
-      p1f(halves[1], side);
-    } else {
-      if (tail) {
-        KS_HIP(hipEventRecord(ctx->ev[12], st));
-        KS_HIP(hipStreamWaitEvent(side, ctx->ev[12], 0));
-        p1tail();
-        KS_HIP(hipGetLastError());
-        KS_HIP(hipEventRecord(ctx->ev[13], side));
-      }
-      p1f(halves[0], st);
-      KS_HIP(hipGetLastError());
-      if (tail) KS_HIP(hipStreamWaitEvent(st, ctx->ev[13], 0));
-    }
-    }
-    KS_HIP(hipGetLastError());
-  } else if (p1summ || exact) {
-    // the tail chunks (a latency-bound serial walk each) run on the side
-    // stream, overlapped with the pipelined pass (of the last half)
-    hipStream_t side = ctx->side;
-    const bool tail = nch > ctail;
-    auto p1p = [&](const Half &h, hipStream_t strm) {
-      const Chunks gv = view(h);
-      const unsigned grid = (unsigned)((h.c1 - h.c0 + kP1Block - 1) / kP1Block);
-      if (lds_lut) {
-        if (J == 5) KS_P1P(5, true, gv, grid, strm); else if (J == 4) KS_P1P(4, true, gv, grid, strm);
-        else if (J == 3) KS_P1P(3, true, gv, grid, strm); else KS_P1P(2, true, gv, grid, strm);
-      } else {
-        if (J == 5) KS_P1P(5, false, gv, grid, strm); else if (J == 4) KS_P1P(4, false, gv, grid, strm);
-        else if (J == 3) KS_P1P(3, false, gv, grid, strm); else KS_P1P(2, false, gv, grid, strm);
-      }
-    };
-    if (split) {
-      // first half on the highest-priority stream, the tail chunks and the
-      // second half on the (lowest-priority) side stream at once: the second
-      // half's blocks fill the CUs the first half leaves, its drain included,
-      // and the first half ends first (its carry and stitch then run under
-      // the rest of the second half; serial halves cost 0.6 ms in-process).
-      KS_HIP(hipEventRecord(ctx->ev[17], st));
-      KS_HIP(hipStreamWaitEvent(ctx->hi, ctx->ev[17], 0));
-      if (!side_forked) KS_HIP(hipStreamWaitEvent(side, ctx->ev[17], 0));
-      p1p(halves[0], ctx->hi);
-      KS_HIP(hipGetLastError());
-      KS_HIP(hipEventRecord(ctx->ev[12], ctx->hi));
-      KS_HIP(hipStreamWaitEvent(st, ctx->ev[12], 0));
-      cand = cands[1];  // (the tail chunks are the second half's)
-      if (tail) {
-        if (J == 5) KS_P1T(5, false);
-        else if (lds_lut) { if (J == 4) KS_P1T(4, true); else if (J == 3) KS_P1T(3, true); else KS_P1T(2, true); }
-        else { if (J == 4) KS_P1T(4, false); else if (J == 3) KS_P1T(3, false); else KS_P1T(2, false); }
-        KS_HIP(hipGetLastError());
-      }
-      p1p(halves[1], side);
-      KS_HIP(hipGetLastError());
-    } else {
-      if (tail) {
-        KS_HIP(hipEventRecord(ctx->ev[12], st));
-        KS_HIP(hipStreamWaitEvent(side, ctx->ev[12], 0));
-        if (J == 5) KS_P1T(5, false);
-        else if (lds_lut) { if (J == 4) KS_P1T(4, true); else if (J == 3) KS_P1T(3, true); else KS_P1T(2, true); }
-        else { if (J == 4) KS_P1T(4, false); else if (J == 3) KS_P1T(3, false); else KS_P1T(2, false); }
-        KS_HIP(hipGetLastError());
-        KS_HIP(hipEventRecord(ctx->ev[13], side));
-      }
-      p1p(halves[0], st);
-      KS_HIP(hipGetLastError());
-      if (tail) KS_HIP(hipStreamWaitEvent(st, ctx->ev[13], 0));
-    }
-  } else if (comp) {
-    KS_P1(1, true, false);  // unexpanded compressed table (with the code store)
+  KS_TRY(record(kEvP1Begin, st));
+
+  // ---- P1 gather pass
+  if (plan.family == P1Family::Plain) {
+    KS_TRY(pick_bool(plan.comp, [&](auto cp) {
+      return launch(k_pass1<1, decltype(cp)::value, false>, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, w.g,
+                    s->seq, c.total, k, tv, w.codes, c.ec, visits, w.p1, w.cands[0], (int64_t)0, 0);
+    }));
+  } else if (plan.rank_alone) {  // every chunk (guarded base loads)
+    const dim3 grid((unsigned)((nch + kRankBlock - 1) / kRankBlock));
+    KS_TRY(pick_bool(k == 15, [&](auto k15) {
+      return launch(k_pass1r<decltype(k15)::value ? 1 : 2>, grid, dim3(kRankBlock), 0, st, w.g, c.total, k, tv, c.ec,
+                    visits, w.p1, w.cands[0]);
+    }));
+  } else if (plan.split) {
+    // first half on the highest-priority stream, the tail chunks and the
+    // second half on the (lowest-priority) side stream at once: the second
+    // half's blocks fill the CUs the first half leaves, its drain included,
+    // and the first half ends first (its carry and stitch then run under
+    // the rest of the second half; serial halves cost 0.6 ms in-process).
+    KS_TRY(record(kEvP1Fork, st));
+    KS_TRY(wait(hi, kEvP1Fork));
+    if (!side_forked) KS_TRY(wait(side, kEvP1Fork));
+    KS_TRY(pass1_half(c, plan, w, plan.half[0], hi, w.cands[0]));
+    KS_TRY(record(kEvP1Half0, hi));
+    KS_TRY(wait(st, kEvP1Half0));
+    if (plan.tail) KS_TRY(pass1_tail(c, plan, w, side, w.cands[1]));  // (the tail chunks are the second half's)
+    KS_TRY(pass1_half(c, plan, w, plan.half[1], side, w.cands[1]));
   } else {
-    KS_P1(1, false, false);  // (expanded FP64 tables take k_pass1pf above)
+    // the tail chunks on the side stream, overlapped with the pipelined pass
+    if (plan.tail) {
+      KS_TRY(record(kEvP1Half0, st));
+      KS_TRY(wait(side, kEvP1Half0));
+      KS_TRY(pass1_tail(c, plan, w, side, w.cands[0]));
+      KS_TRY(record(kEvSideDone, side));
+    }
+    KS_TRY(pass1_half(c, plan, w, plan.half[0], st, w.cands[0]));
+    if (plan.tail) KS_TRY(wait(st, kEvSideDone));
   }
-#undef KS_P1
-#undef KS_P1T
-#undef KS_P1TC
-#undef KS_P1P
-  KS_HIP(hipGetLastError());
   // (the first half's post-processing on the high-priority stream, ahead of
   // the second half's pass-1 blocks, measured the same: 14.15 vs 14.15 ms,
   // profiles/r5/ab/ab_post0.txt)
-  if (split) {
+  if (plan.split) {
     // end of pass 1 = the later of the halves: the hi stream (idle now) joins the side stream's
-    KS_HIP(hipEventRecord(ctx->ev[18], ctx->side));
-    KS_HIP(hipStreamWaitEvent(ctx->hi, ctx->ev[18], 0));
-    KS_HIP(hipEventRecord(ctx->ev[9], ctx->hi));
+    KS_TRY(record(kEvP1Side, side));
+    KS_TRY(wait(hi, kEvP1Side));
+    KS_TRY(record(kEvP1End, hi));
   } else {
-    KS_HIP(hipEventRecord(ctx->ev[9], split ? ctx->side : st));  // end of pass 1 (the last half's stream)
+    KS_TRY(record(kEvP1End, st));
   }
-  // KS_TEST_EPOCH_STALE (tests): the post-processing expects another epoch
-  // than pass 1 stamped -- what it would see reading an earlier call's
-  // pass-1 results -- so the epoch guard must fail the call
-  if (getenv("KS_TEST_EPOCH_STALE")) ++p1.epoch;
+  if (plan.epoch_stale) ++w.p1.epoch;
 
-  // P2-P5 (without the candidates) of one half on stream strm, with its own
-  // replay counter, error bits and fix list; ev[14] / ev[15] mark the last
-  // half's phases
-  auto post = [&](int hi, const Half &h, hipStream_t strm) -> ks_status {
-    const bool last = hi == nhalf - 1;
-    const Chunks gv = view(h);
-    const int64_t nh = h.c1 - h.c0, nr = h.r1 - h.r0, nt = h.t1 - h.t0;
-    if (nh <= 0) return KS_OK;
-    unsigned long long *rep_h = d_replays + 2 * hi;
-    unsigned int *err_h = reinterpret_cast<unsigned int *>(d_replays + 2 * hi + 1);
-    const unsigned gch_h = (unsigned)((nh + 255) / 256);
-    const unsigned gsum_h = (unsigned)((nh + 1023) / 1024);
-    // ---- P2 prediction, segment starts, summaries
-    KS_TRY(ascan(p1, xt, h.r0, h.r1, h.t0, h.t1, strm));
-    const int64_t wl = (h.c0 > 0 ? h.c0 - 1 : 0) / 64;
-    const int64_t nwm = (h.c1 + 63) / 64 - wl;
-    // segment marks and summary selection in one pass over the chunks
-    if (!p1summ && !exact) {
-      hipLaunchKernelGGL(k_seg_marks, dim3((unsigned)((nwm + wpb - 1) / wpb)), dim3(64 * wpb), 0, strm, gv, p1, xt,
-                         d_flag, nwm);
-      KS_HIP(hipGetLastError());
-    }
-    if (exact) {  // the prescan is the carry (k_carry_exact)
-      hipLaunchKernelGGL(k_carry_exact, dim3(gch_h), dim3(256), 0, strm, gv, p1, xt, cr);
-    } else if (p1summ) {
-      KS_HIP(hipMemsetAsync(d_nfix + hi, 0, 8, strm));
-      KS_HIP(hipMemsetAsync(rpb.count + hi, 0, 8, strm));
-      hipLaunchKernelGGL(k_marks_select, dim3((unsigned)((nwm + 3) / 4)), dim3(256), 0, strm, gv, p1, xt, d_flag, nwm,
-                         sp1, sm, d_fix + h.c0, d_nfix + hi, d_xh,
-                         dbg ? reinterpret_cast<unsigned long long *>(dbg + nwin * 9) : nullptr, rpb, hi);
-      KS_HIP(hipGetLastError());
-      // summaries of the listed chunks, a wave each; the LUT read through L2,
-      // not staged in LDS: a 54 KB LDS copy per block (2048 blocks, most
-      // without a listed chunk) cost more than the ~4 M lookups of the ~16 K
-      // listed chunks
-      const unsigned gw = (unsigned)std::max<int64_t>(1, (int64_t)ctx->num_cus * 8);
-      hipLaunchKernelGGL(k_summ_fixw<false>, dim3(gw), dim3(256), 0, strm, g, s->seq, total, k, tv, xt,
-                         d_fix + h.c0, d_nfix + hi, sm, rpb, hi);
-    } else if (no_summ) {
-      hipLaunchKernelGGL(k_summ_none, dim3(gsum_h), dim3(1024), 0, strm, gv, sm);
-    } else if (lds_table) {
-      // small k: the table staged in LDS as for k_pass1_lds (from HBM / L2: 12.8 / 18.7 vs 3.8 / 6.4 ms)
-      if (comp && lds_lut) {
-        const size_t tb = (size_t)2 << (2 * k);
-        KS_HIP(hipFuncSetAttribute((const void *)k_summaries<true, true, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
-        hipLaunchKernelGGL((k_summaries<true, true, true>), dim3(gsum_h), dim3(1024), tb, strm, gv, s->seq, total, k,
-                           tv, nullptr, p1, xt, sm);
-      } else {
-        const size_t tb = (size_t)8 << (2 * k);
-        KS_HIP(hipFuncSetAttribute((const void *)k_summaries<false, false, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb));
-        hipLaunchKernelGGL((k_summaries<false, false, true>), dim3(gsum_h), dim3(1024), tb, strm, gv, s->seq, total,
-                           k, tv, nullptr, p1, xt, sm);
-      }
-    } else if (lds_lut)
-      hipLaunchKernelGGL((k_summaries<true, true>), dim3(gsum_h), dim3(1024), 0, strm, gv, s->seq, total, k, tv, codes,
-                         p1, xt, sm);
-    else if (comp)
-      hipLaunchKernelGGL((k_summaries<true, false>), dim3(gsum_h), dim3(1024), 0, strm, gv, s->seq, total, k, tv, codes,
-                         p1, xt, sm);
-    else
-      hipLaunchKernelGGL((k_summaries<false, false>), dim3(gsum_h), dim3(1024), 0, strm, gv, s->seq, total, k, tv,
-                         codes, p1, xt, sm);
-    KS_HIP(hipGetLastError());
-    if (last) KS_HIP(hipEventRecord(ctx->ev[14], strm));
-
-    // ---- P3 carry by segments + P4 heads; then the gated per-run fallback
-    const int64_t wc = h.c0 / 64;
-    const unsigned nwc = (unsigned)((h.c1 - 1) / 64 - wc + 1);
-    const TileComp tch = tcomp;
-    const unsigned gtc = (unsigned)(((h.c1 - 1) / 64 - wc + 1 + 3) / 4);  // 4 tiles per block
-    if (!exact) {
-      hipLaunchKernelGGL(k_tile_comp, dim3(gtc), dim3(256), 0, strm, gv, sm, tch);
-      KS_HIP(hipGetLastError());
-    }
-    if (exact) {
-    } else if (comp)
-      hipLaunchKernelGGL(k_carry_win<true>, dim3((nwc + wpb - 1) / wpb), dim3(64 * wpb), 0, strm, gv, d_flag, s->seq, total, k, tv, codes, p1,
-                         sm, cr, tch, rpb, rep_h, err_h, dbg);
-    else
-      hipLaunchKernelGGL(k_carry_win<false>, dim3((nwc + wpb - 1) / wpb), dim3(64 * wpb), 0, strm, gv, d_flag, s->seq, total, k, tv, codes,
-                         p1, sm, cr, tch, rpb, rep_h, err_h, dbg);
-    KS_HIP(hipGetLastError());
-    if (!exact) {
-      hipLaunchKernelGGL(k_tile_apply, dim3(gtc), dim3(256), 0, strm, gv, sm, tch, cr, err_h, 0);
-      KS_HIP(hipGetLastError());
-    }
-    // FP64 tables: the R chunks' heads packed densely (k_heads_dense; lane per
-    // chunk, k_heads, measured slower at config 3: 29.9 vs 29.2 ms,
-    // profiles/r5/ab/ab_heads_dense_lane_pf_*.txt); compressed tables: k_heads
-    const bool dense_heads = !comp;
-    auto heads = [&](int gated) {
-      // (gated: a small grid-stride grid; it exits at once unless the carry fell back)
-      const unsigned gd = (unsigned)((nh + 4 * kHeadSpan - 1) / (4 * kHeadSpan));
-      const unsigned gh = gated ? std::min<unsigned>(dense_heads ? gd : gch_h, (unsigned)ctx->num_cus * 2)
-                                : (dense_heads ? gd : gch_h);
-#define KS_HEADS_D(J, W)                                                                                          \
-  hipLaunchKernelGGL((k_heads_dense<J, false, W>), dim3(gh), dim3(256), 0, strm, gv, s->seq, total, k, tv, codes, \
-                     cr, err_h, gated)
-      if (comp) {
-        hipLaunchKernelGGL((k_heads<1, true>), dim3(gh), dim3(256), 0, strm, gv, s->seq, total, k, tv, codes, cr,
-                           err_h, gated);
-      } else if (J == 4 && tv.line) KS_HEADS_D(4, true);
-      else if (J == 4) KS_HEADS_D(4, false);
-      else if (J == 3) KS_HEADS_D(3, false);
-      else if (J == 2) KS_HEADS_D(2, false);
-      else KS_HEADS_D(1, false);
-#undef KS_HEADS_D
-    };
-    heads(0);
-    KS_HIP(hipGetLastError());
-    if (!exact) hipLaunchKernelGGL(k_fallback_prep, dim3(1), dim3(1), 0, strm, err_h, rep_h, force_fb);
-    if (nr > 0 && !exact) {
-      if (comp)
-        hipLaunchKernelGGL(k_carry_run<true>, dim3((unsigned)nr), dim3(64), 0, strm, gv, d_cbase, h.r1, s->seq, total,
-                           k, tv, codes, p1, sm, cr, tch, rpb, rep_h, err_h, nullptr, h.r0);
-      else
-        hipLaunchKernelGGL(k_carry_run<false>, dim3((unsigned)nr), dim3(64), 0, strm, gv, d_cbase, h.r1, s->seq,
-                           total, k, tv, codes, p1, sm, cr, tch, rpb, rep_h, err_h, nullptr, h.r0);
-      hipLaunchKernelGGL(k_tile_apply, dim3(gtc), dim3(256), 0, strm, gv, sm, tch, cr, err_h, 1);
-    }
-    if (!exact) heads(1);
-    KS_HIP(hipGetLastError());
-    if (last) KS_HIP(hipEventRecord(ctx->ev[15], strm));
-
-    // ---- P5 stitch
-    if (nt > 0) {
-      hipLaunchKernelGGL(k_stitch_tiles, dim3((unsigned)((nt + wpb - 1) / wpb)), dim3(64 * wpb), 0, strm, g, d_tbase, d_cbase,
-                         nruns, d_trun, p1, cr, xagg, h.t0, h.t1);
-      KS_HIP(hipGetLastError());
-    }
-    if (nr > 0) {
-      hipLaunchKernelGGL(k_stitch_runs, dim3((unsigned)nr), dim3(64), 0, strm, d_tbase, h.r1, runs.a, runs.b, runs.seq,
-                         ec, xagg, xtin, rb, rss[hi], h.r0);
-      KS_HIP(hipGetLastError());
-    }
-    if (nt > 0) {
-      hipLaunchKernelGGL(k_stitch_emit, dim3((unsigned)((nt + wpb - 1) / wpb)), dim3(64 * wpb), 0, strm, g, d_tbase, d_cbase,
-                         nruns, d_trun, runs.a, runs.seq, p1, cr, ec, xtin, rb, rss[hi], err_h, h.t0, h.t1);
-      KS_HIP(hipGetLastError());
-    }
-    return KS_OK;
-  };
-  // ---- candidates (count read on the device), rescans: of each half's
-  // list on the stream of its post-processing (the first half's under the
-  // second half's, weighted rank: ~3.8 ms of lane walks), on st
-  // (the rescan slots in list order: sorted longest first they took 5.23 vs
-  // 3.56 ms at config 3, profiles/r4/ab2/ab_rank.txt)
-  auto emit_rescan = [&](int h, hipStream_t rst) -> ks_status {
-    hipLaunchKernelGGL(k_candidates, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0, rst, g, runs.a, d_cbase,
-                       nruns, runs.seq, ec, cands[h], cr, rb, rss[h]);
-    KS_HIP(hipGetLastError());
-    if (h == nhalf - 1) KS_HIP(hipEventRecord(ctx->ev[10], rst));
-    KS_TRY(launch_scan_lane(ctx, s->seq, total, rss[h].a, rss[h].b, rss[h].seq, rcap, k, tv, mw, min_score,
-                            visits_rescan, rb, rss[h].count, rss[h].segcap, mode, 0, nullptr, runs.packed, rst));
-    return KS_OK;
-  };
-  if (split) {
+  // ---- P2-P5 per half, then its candidates and rescans on the main stream
+  KS_TRY(post_half(c, plan, w, 0, st));  // two parts: under the second half's pass 1
+  KS_TRY(emit_rescan(c, plan, w, 0, st));
+  if (plan.split) {
     // (the first half's rescans under the second half's post-processing: config 3
-    // 32.1 vs 32.9 ms with both after the join, profiles/r4/ab3/)
-    // (the second half's rescans on the side stream, beside the first half's
-    // instead of after the join: 28.53 vs 28.46 ms at config 3, metric 14.71
-    // vs 14.65, profiles/r5/ab/ab_rescan_side_*.txt)
-    KS_TRY(post(0, halves[0], st));         // under the second half's pass 1
-    KS_TRY(emit_rescan(0, st));             // under the second half's post-processing
-    KS_TRY(post(1, halves[1], ctx->side));
-    KS_HIP(hipEventRecord(ctx->ev[13], ctx->side));
-    KS_HIP(hipStreamWaitEvent(st, ctx->ev[13], 0));
-    KS_TRY(emit_rescan(1, st));
-  } else {
-    KS_TRY(post(0, halves[0], st));
-    KS_TRY(emit_rescan(0, st));
+    // 32.1 vs 32.9 ms with both after the join, profiles/r4/ab3/; the second
+    // half's rescans after the join, not on the side stream beside the first
+    // half's: 28.46 vs 28.53 ms at config 3, metric 14.65 vs 14.71,
+    // profiles/r5/ab/ab_rescan_side_*.txt)
+    KS_TRY(post_half(c, plan, w, 1, side));
+    KS_TRY(record(kEvSideDone, side));
+    KS_TRY(wait(st, kEvSideDone));
+    KS_TRY(emit_rescan(c, plan, w, 1, st));
   }
-  KS_HIP(hipEventRecord(ctx->ev[11], st));
-  // the region counters too (final: the rescans above append the last
-  // regions), copied next to the scan's counters: one readback for both, and
-  // scan_impl needs no round trip of its own
-  hipLaunchKernelGGL(k_copy_u64, dim3(1), dim3(64), 0, st, rb.count, cnts + 2 * kSegs + 8, kSegs);
-  KS_HIP(hipGetLastError());
+  KS_TRY(record(kEvEnd, st));
+
+  // ---- read-back: the scan's counters and the region counters (final: the
+  // rescans above append the last regions) in one copy, so scan_impl needs no
+  // round trip of its own
+  KS_TRY(launch(k_copy_u64, dim3(1), dim3(64), 0, st, rb.count, cnts + 2 * kSegs + 8, kSegs));
   std::vector<unsigned long long> hcv(5 * kSegs + 8);
   KS_HIP(hipMemcpyAsync(hcv.data(), cnts, 8 * (5 * kSegs + 8), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
   std::copy(hcv.begin() + 2 * kSegs + 8, hcv.begin() + 3 * kSegs + 8, ctx->hreg);
   ctx->hreg_ok = true;
-  static const bool verify = getenv("KS_DEBUG_VERIFY") != nullptr;
-  if (verify) debug_verify(ctx, s, total, k, tv, g, p1, cr, exact, mode.trlr);
+  if (plan.debug_verify) debug_verify(c, w);
   unsigned long long cand_max = 0, res_max = 0, res_tot = 0;
   for (int q = 0; q < kSegs; ++q) {
     const unsigned long long c0 = hcv[q], c1 = hcv[3 * kSegs + 8 + q];
     const unsigned long long r0 = hcv[kSegs + q], r1 = hcv[4 * kSegs + 8 + q];
     cand_max = std::max(cand_max, std::max(c0, c1));
     res_max = std::max(res_max, std::max(r0, r1));
-    res_tot += std::min<unsigned long long>(r0, (unsigned long long)rs.segcap) +
-               std::min<unsigned long long>(r1, (unsigned long long)rs.segcap);
+    res_tot += std::min<unsigned long long>(r0, (unsigned long long)rsegcap) +
+               std::min<unsigned long long>(r1, (unsigned long long)rsegcap);
   }
-  // hc: [0] largest candidate segment, [1] rescans, [2] replays, [3] error bits
-  const unsigned long long hc[4] = {cand_max, res_tot, hcv[2 * kSegs] + hcv[2 * kSegs + 2],
-                                     (hcv[2 * kSegs + 1] | hcv[2 * kSegs + 3]) & 0xffffffffull};
-
-  const unsigned int errbits = (unsigned int)(hc[3] & 0xffffffffu);
-  if ((errbits & 16u) && !force_fb)
+  const unsigned long long replays = hcv[2 * kSegs] + hcv[2 * kSegs + 2];
+  const unsigned int errbits = (unsigned int)((hcv[2 * kSegs + 1] | hcv[2 * kSegs + 3]) & 0xffffffffull);
+  if ((errbits & 16u) && !plan.force_fb)
     fprintf(stderr, "kmer_spans_amd: carry segment check failed; the carry was redone per run\n");
-  if (dbg_on && p1summ) {
-    unsigned long long nf = 0;
-    unsigned long long nf2[2] = {0, 0};
-    KS_HIP(hipMemcpy(nf2, d_nfix, 16, hipMemcpyDeviceToHost));
-    nf = nf2[0] + nf2[1];
-    unsigned long long why[3] = {0, 0, 0};
-    KS_HIP(hipMemcpy(why, dbg + nwin * 9, 24, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[p1summ] chunks %lld gathered summaries %llu (no prediction %llu, void %llu, other binade %llu)\n",
-            (long long)nch, nf, why[0], why[1], why[2]);
-    if (rpb.slot) {
-      unsigned long long rc[2] = {0, 0};
-      KS_HIP(hipMemcpy(rc, rpb.count, 16, hipMemcpyDeviceToHost));
-      fprintf(stderr, "[replay prefetch] listed %llu + %llu chunks (cap %lld per half)\n", rc[0], rc[1],
-              (long long)rpb.cap);
-    }
-  }
-  if (dbg) {
-    std::vector<long long> h(nwin * 9);
-    KS_HIP(hipMemcpy(h.data(), dbg, nwin * 9 * sizeof(long long), hipMemcpyDeviceToHost));
-    KS_HIP(hipFree(dbg));
-    std::vector<int64_t> idx(nwin);
-    for (int64_t i = 0; i < nwin; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) { return h[9 * a] > h[9 * b]; });
-    long long tot[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = 0; i < nwin; ++i)
-      for (int q = 0; q < 9; ++q) tot[q] += h[9 * i + q];
-    fprintf(stderr, "[carry] windows %lld (runs %lld) chunks %lld replays %lld (wave-parallel %lld, bases prefetched "
-            "%lld; cycles %lld, in fast tiles %lld, in replays %lld) segments %lld L %lld R %lld\n", (long long)nwin,
-            (long long)nruns, tot[1], tot[2], tot[8] & 0xffffffffLL, tot[8] >> 32, tot[0], tot[6], tot[7], tot[3],
-            tot[4], tot[5]);
-    for (int64_t i = 0; i < std::min<int64_t>(nwin, 8); ++i) {
-      const long long *d = &h[9 * idx[i]];
-      fprintf(stderr, "[carry] window %lld cycles %lld (fast tiles %lld, replays %lld) chunks %lld replays %lld "
-              "segments %lld L %lld R %lld\n", (long long)idx[i], d[0], d[6], d[7], d[1], d[2], d[3], d[4], d[5]);
-    }
-  }
+  if (plan.debug_carry) KS_TRY(debug_carry_report(plan, w, nruns));
+
+  // ---- failures and retries
   if (errbits & 32u)
     return fail(KS_ERR_DEVICE, "chunked scan epoch check failed: the stitch read pass-1 results not written by this "
-                                 "call (epoch %u)", p1.epoch);
+                                 "call (epoch %u)", w.p1.epoch);
   if (errbits & ~16u) return fail(KS_ERR_INTERNAL, "chunked scan consistency check failed (bits %u)", errbits);
   if ((int64_t)cand_max > csegcap) {  // grow the candidate buffers and rerun the pass
     void *grown = nullptr;
@@ -4971,33 +4840,15 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
     KS_TRY(ensure(ctx, SLOT_CHUNK_C, seg * kSegs * 80 + 2048, &grown));
     return KS_INTERNAL_RETRY;
   }
-  if ((int64_t)res_max > rs.segcap) {  // grow the rescan buffer (regions may have overflowed too) and rerun
+  if ((int64_t)res_max > rsegcap) {  // grow the rescan buffer (regions may have overflowed too) and rerun
     ctx->rescan_segcap = (int64_t)(res_max + res_max / 4 + 64);
     return KS_INTERNAL_RETRY;
   }
-  const int64_t nres = (int64_t)hc[1];
-  if (dbg_on && nres > 0) {  // rescan length histogram (log2 buckets)
-    std::vector<int64_t> a(rcap), b(rcap);
-    KS_HIP(hipMemcpy(a.data(), rs.a, rcap * 8, hipMemcpyDeviceToHost));
-    KS_HIP(hipMemcpy(b.data(), rs.b, rcap * 8, hipMemcpyDeviceToHost));
-    long long hist[40] = {0}, tot = 0, mx = 0;
-    for (int64_t i = 0; i < rcap; ++i) {
-      if ((i % rs.segcap) >= (int64_t)hcv[kSegs + i / rs.segcap]) continue;
-      const long long L = b[i] - a[i] - k;
-      tot += L;
-      mx = std::max(mx, L);
-      int e = 0;
-      while (e < 39 && (1LL << (e + 1)) <= L) ++e;
-      ++hist[L > 0 ? e : 0];
-    }
-    fprintf(stderr, "[rescan] n %lld indices %lld max %lld |", (long long)nres, tot, mx);
-    for (int e = 0; e < 40; ++e)
-      if (hist[e]) fprintf(stderr, " 2^%d:%lld", e, hist[e]);
-    fprintf(stderr, "\n");
-  }
+  const int64_t nres = (int64_t)res_tot;
+  if (plan.debug_carry && nres > 0) KS_TRY(debug_rescan_hist(w.rss[0], hcv.data() + kSegs, k, nres));
   if (stats) {  // (phase times: chunked_phase_times, after the call's last sync)
     stats->n_rescan = nres;
-    stats->n_replay = (int64_t)hc[2];
+    stats->n_replay = (int64_t)replays;
   }
   ctx->chunked_events = true;
   return KS_OK;
@@ -5011,12 +4862,12 @@ ks_status chunked_phase_times(ks_ctx *ctx, ks_scan_stats *stats) {
     return KS_OK;
   }
   float ms_lay = 0, ms_p1 = 0, ms_p2 = 0, ms_p34 = 0, ms_p5 = 0, ms_res = 0;
-  KS_HIP(hipEventElapsedTime(&ms_lay, ctx->ev[7], ctx->ev[8]));
-  KS_HIP(hipEventElapsedTime(&ms_p1, ctx->ev[8], ctx->ev[9]));
-  KS_HIP(hipEventElapsedTime(&ms_p2, ctx->ev[9], ctx->ev[14]));
-  KS_HIP(hipEventElapsedTime(&ms_p34, ctx->ev[14], ctx->ev[15]));
-  KS_HIP(hipEventElapsedTime(&ms_p5, ctx->ev[15], ctx->ev[10]));
-  KS_HIP(hipEventElapsedTime(&ms_res, ctx->ev[10], ctx->ev[11]));
+  KS_HIP(hipEventElapsedTime(&ms_lay, ctx->ev[kEvBegin], ctx->ev[kEvP1Begin]));
+  KS_HIP(hipEventElapsedTime(&ms_p1, ctx->ev[kEvP1Begin], ctx->ev[kEvP1End]));
+  KS_HIP(hipEventElapsedTime(&ms_p2, ctx->ev[kEvP1End], ctx->ev[kEvP2End]));
+  KS_HIP(hipEventElapsedTime(&ms_p34, ctx->ev[kEvP2End], ctx->ev[kEvP34End]));
+  KS_HIP(hipEventElapsedTime(&ms_p5, ctx->ev[kEvP34End], ctx->ev[kEvCandEnd]));
+  KS_HIP(hipEventElapsedTime(&ms_res, ctx->ev[kEvCandEnd], ctx->ev[kEvEnd]));
   // (the second part's P2-P5 events can precede the end of the union of the
   // pass-1 launches when it finished first: such a phase counts 0)
   stats->ms_layout = ms_lay;
@@ -5027,5 +4878,174 @@ ks_status chunked_phase_times(ks_ctx *ctx, ks_scan_stats *stats) {
   stats->ms_rescan = ms_res;
   return KS_OK;
 }
+
+// ------------------------------------------------------------ diagnostics
+namespace {
+
+// KS_DEBUG_VERIFY=1: after a chunked scan of a small input (<= 64 Mi bases,
+// k <= 11, kmer_regions mode), the device's packed codes, chunk layout,
+// pass-1 results and carry modes are copied back and checked against a host
+// recomputation from the sequence bytes and the base table; every mismatch
+// goes to stderr with its chunk and both values.  Reads the buffers after the
+// call's last kernel, so a value that is right here but was wrong when a
+// kernel read it points at an ordering edge, one that is wrong here at the
+// kernel that wrote it.
+void debug_verify(const ScanCall &c, const Work &w) {
+  const Chunks &g = w.g;
+  const P1 &p1 = w.p1;
+  const Carry &cr = w.cr;
+  const TableView &tv = c.tv;
+  const int64_t total = c.total, nch = g.nch;
+  const int k = c.k;
+  if (c.mode.trlr || k > 11 || total > ((int64_t)64 << 20) || nch <= 0) return;
+  (void)hipDeviceSynchronize();
+  auto get = [&](auto *dst, const void *src, size_t n) {
+    if (n) (void)hipMemcpy(dst, src, n * sizeof(*dst), hipMemcpyDeviceToHost);
+  };
+  std::vector<uint8_t> seq((size_t)total);
+  get(seq.data(), c.s->seq, (size_t)total);
+  const int64_t nk = (int64_t)1 << (2 * k);
+  std::vector<double> val((size_t)nk);
+  if (tv.compressed) {
+    std::vector<uint16_t> codes((size_t)nk);
+    get(codes.data(), tv.codes, (size_t)nk);
+    std::vector<double> lut((size_t)std::max(tv.nlut, 1));
+    get(lut.data(), tv.lut, (size_t)tv.nlut);
+    for (int64_t i = 0; i < nk; ++i) val[i] = lut[codes[i]];
+  } else {
+    get(val.data(), tv.vals, (size_t)nk);
+  }
+  long long bad = 0;
+  auto report = [&](const char *what, int64_t ch, double got, double want) {
+    if (++bad <= 12)
+      fprintf(stderr, "[verify] chunk %lld of %lld: %s = %.17g, host %.17g\n", (long long)ch, (long long)nch, what, got,
+              want);
+  };
+  std::vector<int64_t> start((size_t)nch);
+  std::vector<int32_t> n((size_t)nch), run((size_t)nch), tbeg((size_t)nch), targ((size_t)nch);
+  std::vector<double> cexit((size_t)nch), tmax((size_t)nch), cx((size_t)nch);
+  std::vector<uint8_t> mode((size_t)nch);
+  get(start.data(), g.start, (size_t)nch);
+  get(n.data(), g.n, (size_t)nch);
+  if (g.packed) {  // the words the chunks read (a part's run pass packs its own range only)
+    const int64_t nw = total / 16 + 1;
+    std::vector<uint32_t> pk((size_t)nw);
+    std::vector<uint8_t> used((size_t)nw, 0);
+    for (int64_t ch = 0; ch < nch; ++ch)
+      for (int64_t q = std::max<int64_t>(0, (start[ch] - k) / 16); q <= (start[ch] + n[ch]) / 16 && q < nw; ++q)
+        used[q] = 1;
+    get(pk.data(), g.packed, (size_t)nw);
+    for (int64_t q = 0; q < nw; ++q) {
+      uint32_t want = 0;
+      for (int b = 0; b < 16; ++b) want |= enc(16 * q + b < total ? seq[16 * q + b] : (uint8_t)'N') << (30 - 2 * b);
+      if (used[q] && pk[q] != want && 16 * q + 16 <= total) report("packed word", q, (double)pk[q], (double)want);
+    }
+  }
+  get(run.data(), g.run, (size_t)nch);
+  get(tbeg.data(), p1.tbeg, (size_t)nch);
+  get(targ.data(), p1.targ, (size_t)nch);
+  get(cexit.data(), p1.cexit, (size_t)nch);
+  get(tmax.data(), p1.tmax, (size_t)nch);
+  get(cx.data(), cr.x, (size_t)nch);
+  get(mode.data(), cr.mode, (size_t)nch);
+  const uint64_t kmask = (uint64_t)nk - 1;
+  for (int64_t ch = 0; ch < nch; ++ch) {
+    // clean trajectory from 0 over indices start .. start + n - 1 (k-mer
+    // ending at index - 1), as P1Lane::step
+    double prev = 0.0, best = 0.0;
+    int beg = -1, arg = 0;
+    for (int i = 0; i < n[ch]; ++i) {
+      const int64_t p = start[ch] + i;
+      uint64_t code = 0;
+      for (int64_t q = p - k; q < p; ++q) code = ((code << 2) | enc(seq[q])) & kmask;
+      const double sv = val[code];
+      const double tt = prev + sv;
+      const double S = tt > 0 ? tt : 0.0;
+      const bool open = (prev == 0) & (S > 0), close = (prev > 0) & (S == 0);
+      const bool up = open | (S > best);
+      best = up ? S : best;
+      arg = up ? i : arg;
+      beg = open ? i : (close ? -1 : beg);
+      prev = S;
+    }
+    auto ne = [](double a, double b) { return memcmp(&a, &b, 8) != 0; };
+    if (ne(cexit[ch], prev)) report("clean exit", ch, cexit[ch], prev);
+    if (prev > 0) {
+      if (tbeg[ch] != beg) report("tail begin", ch, tbeg[ch], beg);
+      if (targ[ch] != arg) report("tail argmax", ch, targ[ch], arg);
+      if (ne(tmax[ch], best)) report("tail max", ch, tmax[ch], best);
+    } else if (tbeg[ch] != -1) {
+      report("tail begin (none)", ch, tbeg[ch], -1);
+    }
+    const bool first = ch == 0 || run[ch - 1] != run[ch];
+    if (first && (mode[ch] != kModeClean || cx[ch] != 0.0)) report("run-first chunk carry mode", ch, mode[ch], kModeClean);
+  }
+  if (bad) fprintf(stderr, "[verify] %lld mismatches in %lld chunks (k %d, %lld bases)\n", bad, (long long)nch, k,
+                   (long long)total);
+}
+
+// KS_DEBUG_CARRY=1: what the summary selection and the carry counted (Work::dbg,
+// freed here), per call and for the eight costliest 64-chunk windows.
+ks_status debug_carry_report(const ScanPlan &plan, Work &w, int64_t nruns) {
+  const int64_t nwin = w.nwin, nch = w.g.nch;
+  if (plan.p1summ) {
+    unsigned long long nf2[2] = {0, 0};
+    KS_HIP(hipMemcpy(nf2, w.nfix, 16, hipMemcpyDeviceToHost));
+    unsigned long long why[3] = {0, 0, 0};
+    KS_HIP(hipMemcpy(why, w.dbg + nwin * 9, 24, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[p1summ] chunks %lld gathered summaries %llu (no prediction %llu, void %llu, other binade %llu)\n",
+            (long long)nch, nf2[0] + nf2[1], why[0], why[1], why[2]);
+    if (w.rpb.slot) {
+      unsigned long long rc[2] = {0, 0};
+      KS_HIP(hipMemcpy(rc, w.rpb.count, 16, hipMemcpyDeviceToHost));
+      fprintf(stderr, "[replay prefetch] listed %llu + %llu chunks (cap %lld per half)\n", rc[0], rc[1],
+              (long long)w.rpb.cap);
+    }
+  }
+  std::vector<long long> h(nwin * 9);
+  KS_HIP(hipMemcpy(h.data(), w.dbg, nwin * 9 * sizeof(long long), hipMemcpyDeviceToHost));
+  KS_HIP(hipFree(w.dbg));
+  w.dbg = nullptr;
+  std::vector<int64_t> idx(nwin);
+  for (int64_t i = 0; i < nwin; ++i) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) { return h[9 * a] > h[9 * b]; });
+  long long tot[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = 0; i < nwin; ++i)
+    for (int q = 0; q < 9; ++q) tot[q] += h[9 * i + q];
+  fprintf(stderr, "[carry] windows %lld (runs %lld) chunks %lld replays %lld (wave-parallel %lld, bases prefetched "
+          "%lld; cycles %lld, in fast tiles %lld, in replays %lld) segments %lld L %lld R %lld\n", (long long)nwin,
+          (long long)nruns, tot[1], tot[2], tot[8] & 0xffffffffLL, tot[8] >> 32, tot[0], tot[6], tot[7], tot[3],
+          tot[4], tot[5]);
+  for (int64_t i = 0; i < std::min<int64_t>(nwin, 8); ++i) {
+    const long long *d = &h[9 * idx[i]];
+    fprintf(stderr, "[carry] window %lld cycles %lld (fast tiles %lld, replays %lld) chunks %lld replays %lld "
+            "segments %lld L %lld R %lld\n", (long long)idx[i], d[0], d[6], d[7], d[1], d[2], d[3], d[4], d[5]);
+  }
+  return KS_OK;
+}
+
+// KS_DEBUG_CARRY=1: length histogram (log2 buckets) of the first list's rescans.
+ks_status debug_rescan_hist(const Rescan &rs, const unsigned long long *counts, int k, int64_t nres) {
+  std::vector<int64_t> a(rs.cap), b(rs.cap);
+  KS_HIP(hipMemcpy(a.data(), rs.a, rs.cap * 8, hipMemcpyDeviceToHost));
+  KS_HIP(hipMemcpy(b.data(), rs.b, rs.cap * 8, hipMemcpyDeviceToHost));
+  long long hist[40] = {0}, tot = 0, mx = 0;
+  for (int64_t i = 0; i < rs.cap; ++i) {
+    if ((i % rs.segcap) >= (int64_t)counts[i / rs.segcap]) continue;
+    const long long L = b[i] - a[i] - k;
+    tot += L;
+    mx = std::max(mx, L);
+    int e = 0;
+    while (e < 39 && (1LL << (e + 1)) <= L) ++e;
+    ++hist[L > 0 ? e : 0];
+  }
+  fprintf(stderr, "[rescan] n %lld indices %lld max %lld |", (long long)nres, tot, mx);
+  for (int e = 0; e < 40; ++e)
+    if (hist[e]) fprintf(stderr, " 2^%d:%lld", e, hist[e]);
+  fprintf(stderr, "\n");
+  return KS_OK;
+}
+
+}  // namespace
 
 }  // namespace ks

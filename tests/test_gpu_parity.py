@@ -585,14 +585,31 @@ def test_trlr_random_vs_oracle(K, oracle):
         assert np.array_equal(r["kmer_scores"][:, 0], ks) and np.array_equal(r["kmer_scores"][:, 1], tr)
 
 
+_SPLIT = {"KS_SPLIT_MIN_CHUNKS": "0"}
+_SPLIT_NOLINES = {"KS_SPLIT_MIN_CHUNKS": "0", "KS_NO_LINES": "1"}
+
+
+@pytest.mark.parametrize("env,second", [({}, 100_000), (_SPLIT, 100_000), (_SPLIT_NOLINES, 100_000),
+                                        (_SPLIT, 600_000), (_SPLIT_NOLINES, 600_000)],
+                         ids=["default", "split", "split-nolines", "split-600k", "split-nolines-600k"])
 @pytest.mark.parametrize("k", [7, 11])
-def test_trlr_device_chunked(K, oracle, ctx, k):
+def test_trlr_device_chunked(K, oracle, ctx, k, env, second, monkeypatch):
     """tr_lr on a human-shaped contig through the device path, the chunked
-    scan (giant and small excursions, rescans) and the lane kernel."""
+    scan (giant and small excursions, rescans) and the lane kernel, on the
+    LDS pass (k = 7), the line pass (k = 11) and, without line tables, the
+    expanded pass.  KS_SPLIT_MIN_CHUNKS=0 allows the two-part scan; it cuts at
+    the first run boundary at or after 0.8 of the chunks (k_split) and only
+    if 2,048 chunks follow the cut.  With the 100 kbp second sequence (391 of
+    ~12 k chunks) only an N gap of the contig could fall there, so those cases
+    ran in one part on the MI355X; the 600 kbp one (2,344 of ~14 k chunks)
+    puts the sequence boundary inside that window, whatever the gaps, and
+    ran in two parts."""
     import torch
     from kmer_spans_amd import device as D, genome
+    for name, value in env.items():  # before the tables: KS_NO_LINES is read at table build
+        monkeypatch.setenv(name, value)
     s = genome.contig(3_000_000, 40 + k, device="cuda", repeats=True)
-    ds = D.from_parts([s, s[:100_000].clone()], [s.numel(), 100_000], "cuda")
+    ds = D.from_parts([s, s[:second].clone()], [s.numel(), second], "cuda")
     host = [ds.host_seq(0), ds.host_seq(1)]
     n, oc = oracle.kmer_counts(host, k)
     tr = np.log2(oc + 1.0) - np.log2(np.median(oc) + 1.0) - 0.4  # repeats score positive
