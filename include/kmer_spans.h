@@ -360,6 +360,52 @@ ks_status ks_scan_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, const ks_
 ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, const ks_table *trans,
                        const ks_table *init, int32_t min_length, ks_regions *out, ks_scan_stats *stats);
 
+/* Sequence index: a handle that lets repeated scans of the same
+ * device-resident sequences reuse the run segmentation, the packed 2-bit
+ * codes and (for the same k and scan kind) the chunk layout of the previous
+ * scan instead of recomputing them from the bytes on every call.
+ *
+ * The handle is a small host object: create does no device work and
+ * allocates no device memory.  It records a process-unique id, seqs->seq,
+ * seqs->offsets_dev, seqs->nseq and a copy of seqs->offsets_host.  What it
+ * indexes lives in the workspace of the context that scanned last: a scan
+ * with the handle is a hit when that context's workspace still holds the
+ * data of the same handle's previous scan, and a build (the work of a plain
+ * call) otherwise -- after a scan of other sequences, a plain scan, a
+ * ks_windowed_dev call, a host-buffer entry point or a release of the
+ * workspace on that context.
+ *
+ * Contract: from create to destroy the caller changes neither the sequence
+ * bytes nor the offsets (host or device).  Changed sequences need a new
+ * index.  A hit call runs a cheap check of the cached runs and of a sample of
+ * the packed codes against the bytes; a mismatch fails the call with
+ * KS_ERR_ARG ("sequence bytes changed under a sequence index"), returns no
+ * regions, counts in guard_failures and makes the next call with the handle
+ * a build.  The check is a tripwire for contract violations, not a proof: a
+ * change inside a run and outside the sampled units passes it.
+ *
+ * The _indexed entries return KS_ERR_ARG when seqs does not match the handle
+ * (pointers, nseq, offsets).  ix == NULL, or KS_NO_SEQ_INDEX set in the
+ * environment (read per call), makes them the plain entries.  ks_scan_dev
+ * and ks_tr_lr_dev always recompute.  On a hit ks_scan_stats.ms_runs is 0. */
+typedef struct ks_seq_index ks_seq_index;
+ks_status ks_seq_index_create(const ks_dev_seqs *seqs, ks_seq_index **out);
+void ks_seq_index_destroy(ks_seq_index *ix);
+typedef struct ks_seq_index_info {
+  int64_t builds;         /* indexed calls that ran the run segmentation            */
+  int64_t hits;           /* indexed calls that reused it                           */
+  int64_t layout_builds;  /* indexed calls that computed the chunk layout (every
+                             build, and a hit with another k or scan kind)          */
+  int64_t guard_failures; /* hit calls failed by the check against the bytes        */
+} ks_seq_index_info;
+ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_info *out);
+ks_status ks_scan_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *seqs, ks_seq_index *ix, int32_t k,
+                              const ks_table *table, int32_t min_width, double min_score, int32_t *visits_dev,
+                              ks_regions *out, ks_scan_stats *stats);
+ks_status ks_tr_lr_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *seqs, ks_seq_index *ix, int32_t k,
+                               const ks_table *trans, const ks_table *init, int32_t min_length, ks_regions *out,
+                               ks_scan_stats *stats);
+
 /* k-mer counting of device-resident sequences into counts_dev (int32[4^k],
  * accumulated: the caller zeroes it).  *n_words as in ks_kmer_counts. */
 ks_status ks_count_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, int32_t *counts_dev,

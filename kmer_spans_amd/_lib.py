@@ -47,6 +47,14 @@ class ScanStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class SeqIndexInfo(C.Structure):
+    _fields_ = [("builds", C.c_int64), ("hits", C.c_int64), ("layout_builds", C.c_int64),
+                ("guard_failures", C.c_int64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 class TableInfo(C.Structure):
     _fields_ = [("k", C.c_int32), ("compressed", C.c_int32), ("positions_per_read", C.c_int32),
                 ("code_bits", C.c_int32), ("distinct", C.c_int64), ("ext_bytes", C.c_int64),
@@ -118,6 +126,8 @@ EXPORTS = [
     "ks_spectra_dist", "ks_spectra_dist_dev", "ks_spectra_cross_dist", "ks_spectra_cross_dist_dev",
     "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
     "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
+    "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get",
+    "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
 ]
 
 KS_SPECTRA_MAX_Q = 6
@@ -204,6 +214,11 @@ def load():
         "ks_hclust": ([P, P, I64, I32, P, P, P], I32),
         "ks_hclust_dev": ([P, P, I64, I32, I32, P, P, P, P], I32),
         "ks_hclust_cut": ([P, P, I64, I32, D, P], I32),
+        "ks_seq_index_create": ([P, P], I32),
+        "ks_seq_index_destroy": ([P], None),
+        "ks_seq_index_info_get": ([P, P], I32),
+        "ks_scan_dev_indexed": ([P, P, P, I32, P, I32, D, P, P, P], I32),
+        "ks_tr_lr_dev_indexed": ([P, P, P, I32, P, P, I32, P, P], I32),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

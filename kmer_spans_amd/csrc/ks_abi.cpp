@@ -173,8 +173,10 @@ void debug_poison(void *p, size_t n) {
 void debug_poison_workspace(ks_ctx *ctx) {
   if (debug_poison_byte() < 0 || !ctx) return;
   for (ks_ctx *c : {ctx, ctx->sub})
-    if (c)
+    if (c) {
+      seq_cache_clear(c);  // (a sequence index's runs and codes are poisoned with the rest)
       for (auto &b : c->slots) debug_poison(b.ptr, b.bytes);
+    }
 }
 
 // The free-ordering probe (diagnostics, tests only).
@@ -210,6 +212,8 @@ void debug_spin_report(const char *where, int slot, double spin_ms, double drain
 ks_status ensure(ks_ctx *ctx, Slot s, size_t bytes, void **out) {
   DevBuf &b = ctx->slots[s];
   if (b.bytes < bytes) {
+    // a sequence index's data does not survive a new buffer for one of its slots
+    if (s == SLOT_PACKED || s == SLOT_RUNS || s == SLOT_LAYOUT) seq_cache_clear(ctx);
     if (b.ptr) {
       // every stream of the context may still use the old buffer (the
       // piecewise count of a host entry runs on the side stream, pass 1's
@@ -349,6 +353,7 @@ extern "C" void ks_ctx_destroy(ks_ctx *c) {
   if (!c) return;
   if (c->pid != getpid()) return;  // inherited across fork(): its HIP handles are not ours
   ks::janitor_forget(c);
+  ks::seq_cache_clear(c);
   if (c->sub) {
     ks_ctx_destroy(c->sub);
     c->sub = nullptr;
@@ -406,7 +411,11 @@ static double idle_ms() {
   return v;
 }
 
+// The one place a context's slots go back to the driver while it lives: the
+// end of a host call under policy 0, the janitor's reclaim (under its lock
+// and the context's ownership word) and ks_release_cache.
 static void free_workspace(ks_ctx *c) {
+  seq_cache_clear(c);
   (void)hipSetDevice(c->device);
   bool any = false;
   for (auto &b : c->slots) any = any || b.ptr;
@@ -696,6 +705,84 @@ extern "C" ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *s, int32_t k, 
   memset(out, 0, sizeof(*out));
   KS_ENTER(ctx);
   ScanMode mode;
+  mode.trlr = 1;
+  mode.ks = init->d_vals;
+  mode.min_len = min_length;
+  mode.finite = trans->no_nan_posinf && init->no_nan_posinf;
+  mode.maxabs = std::max(trans->max_abs, init->max_abs);
+  return scan_impl(ctx, s, s->offsets_host[s->nseq], k, trans, 0, 0.0, nullptr, out, stats, mode);
+}
+
+// ---- sequence index (include/kmer_spans.h)
+static std::atomic<uint64_t> g_seq_index_id{0};
+
+extern "C" ks_status ks_seq_index_create(const ks_dev_seqs *s, ks_seq_index **out) {
+  if (!out) return fail(KS_ERR_ARG, "null output");
+  *out = nullptr;
+  KS_TRY(check_dev_seqs(s));
+  ks_seq_index *ix = new ks_seq_index();
+  ix->id = ++g_seq_index_id;
+  ix->seq = static_cast<const uint8_t *>(s->seq);
+  ix->offsets_dev = s->offsets_dev;
+  ix->nseq = s->nseq;
+  ix->offsets.assign(s->offsets_host, s->offsets_host + s->nseq + 1);
+  *out = ix;
+  return KS_OK;
+}
+
+extern "C" void ks_seq_index_destroy(ks_seq_index *ix) { delete ix; }
+
+extern "C" ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_info *out) {
+  if (!ix || !out) return fail(KS_ERR_ARG, "null argument");
+  out->builds = ix->builds;
+  out->hits = ix->hits;
+  out->layout_builds = ix->layout_builds;
+  out->guard_failures = ix->guard_failures;
+  return KS_OK;
+}
+
+// The index of an _indexed call: nullptr (a plain call) without a handle or
+// under KS_NO_SEQ_INDEX (read per call); KS_ERR_ARG when seqs is not what the
+// handle was created for.
+static ks_status seq_index_of(const ks_dev_seqs *s, ks_seq_index *ix, ks_seq_index **use) {
+  *use = nullptr;
+  if (!ix || getenv("KS_NO_SEQ_INDEX") != nullptr) return KS_OK;
+  if (static_cast<const uint8_t *>(s->seq) != ix->seq || s->offsets_dev != ix->offsets_dev || s->nseq != ix->nseq ||
+      memcmp(s->offsets_host, ix->offsets.data(), sizeof(int64_t) * (size_t)(s->nseq + 1)) != 0)
+    return fail(KS_ERR_ARG, "the sequences do not match the sequence index (pointers, nseq or offsets differ)");
+  *use = ix;
+  return KS_OK;
+}
+
+extern "C" ks_status ks_scan_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *s, ks_seq_index *ix, int32_t k,
+                                         const ks_table *t, int32_t min_width, double min_score,
+                                         int32_t *visits_dev, ks_regions *out, ks_scan_stats *stats) {
+  if (!ctx || !t || !out) return fail(KS_ERR_ARG, "null argument");
+  KS_TRY(check_dev_seqs(s));
+  if (k < 1 || k > KS_MAX_K)
+    return fail(KS_ERR_ARG, "kmer sizes larger than or equal to %d not currently supported", KS_MAX_K + 1);
+  if (t->k != k) return fail(KS_ERR_ARG, "table built for k=%d used with k=%d", t->k, k);
+  memset(out, 0, sizeof(*out));
+  ScanMode mode;
+  KS_TRY(seq_index_of(s, ix, &mode.index));
+  KS_ENTER(ctx);
+  return scan_impl(ctx, s, s->offsets_host[s->nseq], k, t, min_width, min_score, visits_dev, out, stats, mode);
+}
+
+extern "C" ks_status ks_tr_lr_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *s, ks_seq_index *ix, int32_t k,
+                                          const ks_table *trans, const ks_table *init, int32_t min_length,
+                                          ks_regions *out, ks_scan_stats *stats) {
+  if (!ctx || !trans || !init || !out) return fail(KS_ERR_ARG, "null argument");
+  KS_TRY(check_dev_seqs(s));
+  if (k < 1 || k > KS_MAX_K) return fail(KS_ERR_ARG, "k should be a positive value less than MAX_K");
+  if (min_length < 0) return fail(KS_ERR_ARG, "min_length should be a positive integer");
+  if (trans->k != k || init->k != k) return fail(KS_ERR_ARG, "tables built for another k");
+  if (!init->d_vals || init->thr != 0.0 || trans->thr != 0.0)
+    return fail(KS_ERR_ARG, "tr_lr tables need threshold 0 and an uncompressed init table");
+  memset(out, 0, sizeof(*out));
+  ScanMode mode;
+  KS_TRY(seq_index_of(s, ix, &mode.index));
+  KS_ENTER(ctx);
   mode.trlr = 1;
   mode.ks = init->d_vals;
   mode.min_len = min_length;

@@ -77,6 +77,7 @@ constexpr int kScEvents = 0;       // find_runs: run-event count
 constexpr int kScWords = 1;        // launch_count: words counted
 constexpr int kScLayout = 8;       // run_layout: 8 aggregates [8, 16)
 constexpr int kScRegions = 16;     // scan_core: region counters [16, 16 + kSegs)
+constexpr int kScGuard = 80;       // scan_core: the sequence index guard's flag (right after the region counters)
 constexpr int kScSumWords = 96;    // count_words: sum of a histogram
 constexpr int kScMultiWords = 104; // launch_count_multi: words per k of a batch [104, 112)
 constexpr int kScDistBad = 112;    // dist_impl: first bad row index of each selection [112, 114)
@@ -86,6 +87,48 @@ constexpr int kScEnd = 115;
 struct DevBuf {
   void *ptr = nullptr;
   size_t bytes = 0;
+};
+
+// Run table produced by run segmentation: maximal N-free runs [a, b) inside
+// one sequence (SoA).
+struct Runs {
+  int64_t *a = nullptr;
+  int64_t *b = nullptr;
+  int32_t *seq = nullptr;
+  int64_t n = 0;
+  // optional: enc() of every byte, 16 per word, first base most significant
+  // (word p >> 4, bits 30 - 2 * (p & 15)); total / 16 + 1 words
+  const uint32_t *packed = nullptr;
+};
+
+// Scan indices per chunk of the chunked scan, chunks per stitch tile.
+constexpr int kChunk = 256;
+constexpr int kTileChunks = 64;
+
+// Chunk layout of the runs, computed on the device (run_layout): chunk and
+// tile bases per run (device, n + 1 entries) and host totals.
+struct RunLayout {
+  int64_t *cbase = nullptr;
+  int64_t *tbase = nullptr;
+  int64_t nch = 0, ntiles = 0;
+  int64_t scored = 0;   // scan indices (sum over runs of len - k)
+  int64_t nscan = 0;    // runs longer than k
+  int64_t longest = 0;  // longest run (bases)
+  // split of the runs into two halves of about nch / 2 chunks (the chunked
+  // scan overlaps the second half's pass 1 with the first half's later
+  // passes): runs [0, split_r), chunks [0, split_c), tiles [0, split_t)
+  int64_t split_r = 0, split_c = 0, split_t = 0;
+};
+
+// What a context's SLOT_PACKED / SLOT_RUNS / SLOT_LAYOUT hold of a sequence
+// index (ks_seq_index): the last indexed scan's run table and chunk layout.
+// id 0: nothing (the slots hold a plain call's data or were freed, regrown
+// or poisoned since).  seq_cache_clear is the only way the tag goes away.
+struct SeqCache {
+  uint64_t id = 0;  // ks_seq_index::id
+  Runs runs;
+  RunLayout lay;
+  int k = 0, trlr = 0;  // what lay was built for
 };
 
 }  // namespace ks
@@ -116,12 +159,26 @@ struct ks_ctx {
   ks_ctx *sub = nullptr;       // second context of the same device (host entries' table / count / output copies)
   unsigned long long hreg[64] = {};  // region counters per segment read back with the chunked scan's counters
   bool hreg_ok = false;              // (kSegs entries, valid until the next scan attempt)
+  unsigned long long hguard = 0;     // the sequence index guard's flag, read back with hreg
   int64_t rescan_segcap = 0;  // grow-only rescan capacity per segment (tr_lr rescans outnumber regions)
   // top-level visits counted by another context concurrently with the scan
   // (scan_impl): scan_core leaves the count out and says whether it did
   bool vis_count_ext = false;
   bool chunked_events = false;  // the last scan_chunked recorded its phase events (ev[7..11], ev[14..15])
   bool vis_count_ext_used = false;
+  ks::SeqCache seq_cache;  // (ks_runs.hip: find_runs / run_layout; cleared wherever the three slots go)
+};
+
+// A sequence index (include/kmer_spans.h): a host record of which sequences
+// a caller promises not to change, and counters.  The data it indexes lives
+// in a context's slots (ks::SeqCache).
+struct ks_seq_index {
+  uint64_t id = 0;  // process-unique, never 0
+  const uint8_t *seq = nullptr;
+  const int64_t *offsets_dev = nullptr;
+  int32_t nseq = 0;
+  std::vector<int64_t> offsets;  // copy of offsets_host
+  int64_t builds = 0, hits = 0, layout_builds = 0, guard_failures = 0;
 };
 
 struct ks_table {
@@ -341,47 +398,29 @@ ks_status broker_kmers_to_file(const char *seq_path, const char *out_prefix, con
 __host__ __device__ __forceinline__ bool is_n(uint8_t c) { return (c | 0x20) == 'n'; }
 __host__ __device__ __forceinline__ uint32_t enc(uint8_t c) { return (c >> 1) & 3u; }
 
-// Run table produced by run segmentation: maximal N-free runs [a, b) inside
-// one sequence (SoA).
-struct Runs {
-  int64_t *a = nullptr;
-  int64_t *b = nullptr;
-  int32_t *seq = nullptr;
-  int64_t n = 0;
-  // optional: enc() of every byte, 16 per word, first base most significant
-  // (word p >> 4, bits 30 - 2 * (p & 15)); total / 16 + 1 words
-  const uint32_t *packed = nullptr;
-};
-
-// Scan indices per chunk of the chunked scan, chunks per stitch tile.
-constexpr int kChunk = 256;
-constexpr int kTileChunks = 64;
-
-// Chunk layout of the runs, computed on the device (run_layout): chunk and
-// tile bases per run (device, n + 1 entries) and host totals.
-struct RunLayout {
-  int64_t *cbase = nullptr;
-  int64_t *tbase = nullptr;
-  int64_t nch = 0, ntiles = 0;
-  int64_t scored = 0;   // scan indices (sum over runs of len - k)
-  int64_t nscan = 0;    // runs longer than k
-  int64_t longest = 0;  // longest run (bases)
-  // split of the runs into two halves of about nch / 2 chunks (the chunked
-  // scan overlaps the second half's pass 1 with the first half's later
-  // passes): runs [0, split_r), chunks [0, split_c), tiles [0, split_t)
-  int64_t split_r = 0, split_c = 0, split_t = 0;
-};
 // trlr: one more scan index per run (the first k-mer's own step) and the
 // :341 skip of runs whose first k-mer ends within two bytes of the string end.
+// index_id != 0: at the end the context's SeqCache is tagged with it (runs,
+// the layout, k and trlr); the tag is cleared at the top in any case.
 ks_status run_layout(ks_ctx *ctx, const Runs &runs, int k, RunLayout *lay, int trlr = 0,
-                     const int64_t *offs_dev = nullptr);
+                     const int64_t *offs_dev = nullptr, uint64_t index_id = 0);
+// The context's SLOT_PACKED / SLOT_RUNS / SLOT_LAYOUT no longer hold what
+// ctx->seq_cache says: called at the top of find_runs and run_layout and
+// wherever those slots are freed, regrown or poisoned.
+inline void seq_cache_clear(ks_ctx *ctx) { ctx->seq_cache = SeqCache(); }
+// Hit path of a sequence index: checks the cached runs (ends against the
+// bytes and the offsets) and one packed word per 64 KiB against the bytes, on
+// ctx->stream; a mismatch stores 1 to *flag_dev (zeroed by the caller in
+// stream order).  No synchronisation.
+ks_status launch_seq_guard(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, const Runs &runs,
+                           unsigned long long *flag_dev);
 
 // Region record buffer written by scan kernels.
 // Append buffers (regions, rescans, candidates) are split into kSegs
 // segments of segcap slots, each with its own counter, so that appends from
 // thousands of waves do not serialise on one address; slot s*segcap + i.
 constexpr int kSegs = 64;
-static_assert(kScRegions + kSegs <= kScSumWords && kScEnd * 8 <= 4096, "SLOT_SCALARS layout");
+static_assert(kScGuard == kScRegions + kSegs && kScGuard < kScSumWords && kScEnd * 8 <= 4096, "SLOT_SCALARS layout");
 static_assert(kSegs <= 64, "ks_ctx::hreg holds kSegs counters");
 
 struct RegionBuf {
@@ -428,6 +467,8 @@ struct ScanMode {
   // (sequence_kmer_count's histogram, e.g. the one the caller built the
   // table's hint from): the scan applies its corrections and rescans only
   bool visits_counted = false;
+  // sequence index of an _indexed entry (nullptr: a plain call, always recomputes)
+  ks_seq_index *index = nullptr;
 };
 
 ks_status scan_impl(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int k, const ks_table *t,

@@ -280,12 +280,67 @@ __global__ void k_split(const int64_t *__restrict__ cbase, const int64_t *__rest
   out[4] = (unsigned long long)tbase[n];
 }
 
+// Sequence index guard (hit path): thread i < nruns checks run i -- inside
+// the buffer, its first and last byte not N, and each end at the buffer's
+// end, next to an N or at an offset of its sequence; the other threads check
+// one full 16-byte unit in every kGuardStride units (64 KiB of bytes): the
+// packed word recomputed from the bytes equals packed[u].  Any mismatch
+// stores 1 to *flag (every failing lane stores the same value).
+constexpr int64_t kGuardStride = 4096;
+__global__ void __launch_bounds__(256) k_seq_guard(const uint8_t *__restrict__ seq, int64_t total,
+                                                   const int64_t *__restrict__ offs, int32_t nseq,
+                                                   const int64_t *__restrict__ ra, const int64_t *__restrict__ rb,
+                                                   const int32_t *__restrict__ rs, int64_t nruns,
+                                                   const uint32_t *__restrict__ packed, int64_t nsamples,
+                                                   unsigned long long *__restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < nruns) {
+    const int64_t a = ra[i], b = rb[i];
+    const int32_t q = rs[i];
+    if (a < 0 || b <= a || b > total || q < 0 || q >= nseq) {
+      bad = true;
+    } else {
+      const int64_t qa = offs[q], qb = offs[q + 1];
+      bad = a < qa || b > qb || is_n(seq[a]) || is_n(seq[b - 1]) ||
+            !(a == 0 || a == qa || is_n(seq[a - 1])) || !(b == total || b == qb || is_n(seq[b]));
+    }
+  } else if (i - nruns < nsamples) {
+    const int64_t u = (i - nruns) * kGuardStride;  // (the caller counts full units only: 16 u + 16 <= total)
+    const uint4 v = *reinterpret_cast<const uint4 *>(seq + u * 16);
+    const uint32_t w = (enc_pack4m(v.x) << 24) | (enc_pack4m(v.y) << 16) | (enc_pack4m(v.z) << 8) | enc_pack4m(v.w);
+    bad = w != packed[u];
+  }
+  if (bad) *flag = 1ull;
+}
+
 }  // namespace
 
-ks_status run_layout(ks_ctx *ctx, const Runs &runs, int k, RunLayout *lay, int trlr, const int64_t *offs_dev) {
+ks_status launch_seq_guard(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, const Runs &runs,
+                           unsigned long long *flag_dev) {
+  const int64_t full = total / 16;  // full 16-byte units
+  const int64_t nsamples = runs.packed ? (full + kGuardStride - 1) / kGuardStride : 0;
+  const int64_t nthr = runs.n + nsamples;
+  if (nthr <= 0) return KS_OK;
+  hipLaunchKernelGGL(k_seq_guard, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ctx->stream, s->seq, total,
+                     s->offsets_dev, s->nseq, runs.a, runs.b, runs.seq, runs.n, runs.packed, nsamples, flag_dev);
+  KS_HIP(hipGetLastError());
+  return KS_OK;
+}
+
+ks_status run_layout(ks_ctx *ctx, const Runs &runs, int k, RunLayout *lay, int trlr, const int64_t *offs_dev,
+                     uint64_t index_id) {
+  seq_cache_clear(ctx);
   hipStream_t st = ctx->stream;
   const int64_t n = runs.n;
   *lay = RunLayout{};
+  auto tag = [&]() {  // (an _indexed call: the slots now hold this index's runs and layout)
+    if (index_id) ctx->seq_cache = SeqCache{index_id, runs, *lay, k, trlr};
+  };
+  if (n == 0) {  // no run at all: nothing to lay out
+    tag();
+    return KS_OK;
+  }
   void *buf = nullptr;
   KS_TRY(ensure(ctx, SLOT_LAYOUT, (size_t)(n + 1) * 8 * 4 + 256, &buf));
   int64_t *cnt_c = static_cast<int64_t *>(buf);
@@ -322,11 +377,13 @@ ks_status run_layout(ks_ctx *ctx, const Runs &runs, int k, RunLayout *lay, int t
   lay->split_r = (int64_t)ha[3];
   lay->split_c = (int64_t)ha[4];
   lay->split_t = (int64_t)ha[5];
+  tag();
   return KS_OK;
 }
 
 ks_status find_runs(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, Runs *runs, float *ms, bool want_packed,
                     int64_t p_lo, int64_t p_hi) {
+  seq_cache_clear(ctx);  // the run and packed slots are rewritten below, for every caller
   if (p_hi < 0) p_hi = total;
   hipStream_t st = ctx->stream;
   KS_HIP(hipEventRecord(ctx->ev[0], st));

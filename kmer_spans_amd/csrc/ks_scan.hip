@@ -342,11 +342,34 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
   *S = ks_scan_stats{};
   KS_HIP(hipEventRecord(ctx->ev[2], st));
   Runs runs;
-  // (no timing sync here: the run phase's events are read after the call's last sync)
-  KS_TRY(find_runs(ctx, s, total, &runs, nullptr, /*want_packed=*/true));
-  // chunk layout, statistics and algorithm choice (device-side, one sync)
   RunLayout lay;
-  if (runs.n) KS_TRY(run_layout(ctx, runs, k, &lay, mode.trlr, s->offsets_dev));
+  // Sequence index (an _indexed entry): a hit when the context's slots still
+  // hold this index's runs and packed codes -- no find_runs, and no
+  // run_layout either when k and the scan kind are the cached layout's.  The
+  // guard below then checks what was reused against the bytes.
+  ks_seq_index *ix = mode.index;
+  const uint64_t ixid = ix ? ix->id : 0;
+  const bool hit = ixid != 0 && ctx->seq_cache.id == ixid;
+  if (hit) {
+    const SeqCache sc = ctx->seq_cache;  // (run_layout clears the record first)
+    runs = sc.runs;
+    ++ix->hits;
+    if (sc.k == k && sc.trlr == mode.trlr) {
+      lay = sc.lay;
+    } else {
+      KS_TRY(run_layout(ctx, runs, k, &lay, mode.trlr, s->offsets_dev, ixid));
+      ++ix->layout_builds;
+    }
+  } else {
+    // (no timing sync here: the run phase's events are read after the call's last sync)
+    KS_TRY(find_runs(ctx, s, total, &runs, nullptr, /*want_packed=*/true));
+    // chunk layout, statistics and algorithm choice (device-side, one sync)
+    KS_TRY(run_layout(ctx, runs, k, &lay, mode.trlr, s->offsets_dev, ixid));
+    if (ix) {
+      ++ix->builds;
+      ++ix->layout_builds;
+    }
+  }
   const int64_t longest = lay.longest, scored = lay.scored;
   S->n_scored = scored;
   S->n_runs = lay.nscan;
@@ -382,20 +405,30 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
   void *scal = nullptr;
   KS_TRY(ensure(ctx, SLOT_SCALARS, 4096, &scal));
   unsigned long long *d_rcount = reinterpret_cast<unsigned long long *>(scal) + kScRegions;  // [kSegs]
-  std::vector<unsigned long long> hcnt(kSegs, 0);
+  // the sequence index guard's flag follows the region counters (kScGuard)
+  // and comes back with them: no readback of its own
+  std::vector<unsigned long long> hcnt(kSegs + 1, 0);
+  auto guard_failed = [&]() -> ks_status {
+    seq_cache_clear(ctx);  // the same handle recomputes on its next call
+    ++ix->guard_failures;
+    return fail(KS_ERR_ARG, "sequence bytes changed under a sequence index (the cached runs or packed codes no "
+                            "longer match them): create a new index after changing sequences");
+  };
   auto read_counts = [&]() -> ks_status {  // -> hcnt (sync), or the copy the chunked scan made
     if (ctx->hreg_ok) {
       ctx->hreg_ok = false;
       std::copy(ctx->hreg, ctx->hreg + kSegs, hcnt.begin());
-      return KS_OK;
+      hcnt[kSegs] = ctx->hguard;
+    } else {
+      KS_HIP(hipMemcpyAsync(hcnt.data(), d_rcount, 8 * (kSegs + 1), hipMemcpyDeviceToHost, st));
+      KS_HIP(hipStreamSynchronize(st));
     }
-    KS_HIP(hipMemcpyAsync(hcnt.data(), d_rcount, 8 * kSegs, hipMemcpyDeviceToHost, st));
-    KS_HIP(hipStreamSynchronize(st));
+    if (hit && hcnt[kSegs] != 0) return guard_failed();
     return KS_OK;
   };
   auto max_count = [&]() {
     unsigned long long m = 0;
-    for (auto c : hcnt) m = std::max(m, c);
+    for (int q = 0; q < kSegs; ++q) m = std::max(m, hcnt[q]);
     return (int64_t)m;
   };
   RegionBuf rb{};
@@ -412,8 +445,10 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
     rb.count = d_rcount;
     rb.cap = cap;
     rb.segcap = segcap;
-    KS_HIP(hipMemsetAsync(d_rcount, 0, 8 * kSegs, st));
+    KS_HIP(hipMemsetAsync(d_rcount, 0, 8 * (kSegs + 1), st));  // (+ the guard's flag)
     ctx->hreg_ok = false;
+    ctx->hguard = 0;
+    if (hit) KS_TRY(launch_seq_guard(ctx, s, total, runs, d_rcount + kSegs));
     KS_HIP(hipEventRecord(ctx->ev[3], st));
     if (algo == 1) {
       // visits of the chunked path go to a scratch histogram first, so that a
@@ -432,6 +467,8 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
       const bool vis_atomic = getenv("KS_VISITS_ATOMIC") != nullptr;
       ks_status rc = scan_chunked(ctx, s, runs, lay, k, tv, mw, min_score, vis_atomic ? vscr : nullptr, vscr, rb, S,
                                   mode);
+      // (stale runs can make any of the scan's own checks fail: the guard's verdict first)
+      if (hit && ctx->hreg_ok && ctx->hguard != 0) return guard_failed();
       if (rc == KS_INTERNAL_RETRY) {  // a buffer did not fit: grow, rerun, visits untouched
         KS_TRY(read_counts());
         const int64_t m = max_count();
@@ -567,7 +604,7 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
     KS_HIP(hipStreamSynchronize(st));
   }
   S->n_regions = n;
-  {
+  if (!hit) {  // (a hit recorded no run phase: S->ms_runs stays 0, events 0 and 1 are another call's)
     float ms_runs = 0;
     KS_HIP(hipEventElapsedTime(&ms_runs, ctx->ev[0], ctx->ev[1]));  // (find_runs' events)
     S->ms_runs = ms_runs;

@@ -2668,8 +2668,11 @@ __device__ __forceinline__ void select_append(bool want, bool rwant, int64_t c, 
   }
 }
 
-__global__ void k_copy_u64(const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst, int n) {
+// dst[0, n) = src[0, n), and *dst1 = src[n] (the word after the region counters: kScGuard)
+__global__ void k_copy_u64(const unsigned long long *__restrict__ src, unsigned long long *__restrict__ dst, int n,
+                           unsigned long long *__restrict__ dst1) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+  if (threadIdx.x == 0) *dst1 = src[n];
 }
 
 // k_seg_marks and the summary selection in one pass (a wave per 64-chunk window from
@@ -4228,6 +4231,7 @@ struct Work {
   Carry cr;
   // cnts: [0, kSegs) candidate counters, [kSegs, 2 kSegs) rescan counters,
   // [2 kSegs + 2h] replays, [2 kSegs + 2h + 1] error bits (u32) of half h,
+  // [2 kSegs + 4] the copy of the sequence index guard's flag,
   // [2 kSegs + 8, 3 kSegs + 8) the region counters' copy, [3 kSegs + 8,
   // 5 kSegs + 8) the second half's candidate and rescan counters
   unsigned long long *cnts;
@@ -4807,11 +4811,14 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   // ---- read-back: the scan's counters and the region counters (final: the
   // rescans above append the last regions) in one copy, so scan_impl needs no
   // round trip of its own
-  KS_TRY(launch(k_copy_u64, dim3(1), dim3(64), 0, st, rb.count, cnts + 2 * kSegs + 8, kSegs));
+  // (with them the sequence index guard's flag, the word after the region counters: kScGuard)
+  static_assert(kScGuard == kScRegions + kSegs, "the guard's flag follows the region counters");
+  KS_TRY(launch(k_copy_u64, dim3(1), dim3(64), 0, st, rb.count, cnts + 2 * kSegs + 8, kSegs, cnts + 2 * kSegs + 4));
   std::vector<unsigned long long> hcv(5 * kSegs + 8);
   KS_HIP(hipMemcpyAsync(hcv.data(), cnts, 8 * (5 * kSegs + 8), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
   std::copy(hcv.begin() + 2 * kSegs + 8, hcv.begin() + 3 * kSegs + 8, ctx->hreg);
+  ctx->hguard = hcv[2 * kSegs + 4];
   ctx->hreg_ok = true;
   if (plan.debug_verify) debug_verify(c, w);
   unsigned long long cand_max = 0, res_max = 0, res_tot = 0;

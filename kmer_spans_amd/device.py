@@ -18,11 +18,61 @@ from . import _lib
 from ._lib import DevSeqs, Fasta, Regions, ScanStats, SpectraStats, check, load, regions_to_numpy
 
 
+class SeqIndex:
+    """A ks_seq_index handle: lets repeated scans of the same device-resident
+    sequences reuse the previous scan's run segmentation and packed codes (see
+    include/kmer_spans.h for the contract: the bytes and offsets do not change
+    while the handle lives).  Holds no device memory."""
+
+    def __init__(self, s: DevSeqs):
+        self._h = C.c_void_p()
+        check(load().ks_seq_index_create(C.byref(s), C.byref(self._h)))
+
+    def info(self) -> dict:
+        inf = _lib.SeqIndexInfo()
+        check(load().ks_seq_index_info_get(self._h, C.byref(inf)))
+        return inf.as_dict()
+
+    def close(self):
+        if self._h:
+            load().ks_seq_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class DeviceSeqs:
     seq: torch.Tensor          # uint8 [total + pad] on cuda
     offsets: np.ndarray        # int64 [nseq + 1] host
     offsets_dev: torch.Tensor  # int64 [nseq + 1] on cuda
+
+    def seq_index(self) -> SeqIndex:
+        """The sequence index of these sequences, created on first use and
+        again whenever a tensor was replaced or written in place through torch
+        (its version counter moved) or the host offsets changed -- so a torch
+        write to ds.seq gives a new index, and the next scan recomputes."""
+        key = (self.seq.data_ptr(), self.seq._version, self.offsets_dev.data_ptr(), self.offsets_dev._version,
+               self.offsets.tobytes())
+        if getattr(self, "_index_key", None) != key:
+            old = getattr(self, "_index", None)
+            if old is not None:
+                old.close()
+            self._index = SeqIndex(self.struct())
+            self._index_key = key
+        return self._index
+
+    def __del__(self):
+        try:
+            ix = getattr(self, "_index", None)
+            if ix is not None:
+                ix.close()
+        except Exception:  # (interpreter shutdown: the module globals may be gone)
+            pass
 
     @property
     def nseq(self) -> int:
@@ -202,28 +252,31 @@ def _order(ctx) -> None:
 
 def scan(ctx: _lib.Context, ds: DeviceSeqs, k: int, table: DeviceTable, min_width: int, min_score: float,
          visits: torch.Tensor | None = None):
-    """ks_scan_dev: returns (pos int32[3, R], score float64[2, R], stats dict)."""
+    """ks_scan_dev_indexed with ds's sequence index (repeated scans of one ds
+    reuse its run segmentation): returns (pos int32[3, R], score float64[2, R],
+    stats dict)."""
     st = ScanStats()
     r = Regions()
     s = ds.struct()
     _order(ctx)
-    check(load().ks_scan_dev(ctx.handle, C.byref(s), int(k), table._h, int(min_width), float(min_score),
-                             C.c_void_p(visits.data_ptr()) if visits is not None else None, C.byref(r),
-                             C.byref(st)))
+    check(load().ks_scan_dev_indexed(ctx.handle, C.byref(s), ds.seq_index()._h, int(k), table._h, int(min_width),
+                                     float(min_score),
+                                     C.c_void_p(visits.data_ptr()) if visits is not None else None, C.byref(r),
+                                     C.byref(st)))
     pos, score = regions_to_numpy(r)
     return pos, score, st.as_dict()
 
 
 def tr_lr(ctx: _lib.Context, ds: DeviceSeqs, k: int, trans: DeviceTable, init: DeviceTable, min_length: int):
-    """ks_tr_lr_dev: tr_lr regions (1-based, as tr_lr_regions_r) of
+    """ks_tr_lr_dev_indexed: tr_lr regions (1-based, as tr_lr_regions_r) of
     device-resident sequences; trans / init tables with threshold 0 (init
     built with compress=False).  Returns (pos int32[3, R], score float64[2, R], stats)."""
     st = ScanStats()
     r = Regions()
     s = ds.struct()
     _order(ctx)
-    check(load().ks_tr_lr_dev(ctx.handle, C.byref(s), int(k), trans._h, init._h, int(min_length), C.byref(r),
-                              C.byref(st)))
+    check(load().ks_tr_lr_dev_indexed(ctx.handle, C.byref(s), ds.seq_index()._h, int(k), trans._h, init._h,
+                                      int(min_length), C.byref(r), C.byref(st)))
     pos, score = regions_to_numpy(r)
     return pos, score, st.as_dict()
 
@@ -253,6 +306,14 @@ class FastaSeqs:
         self.bases_kept = int(f.bases_kept)
         self.ms_upload = float(f.ms_upload)
         self.ms_parse = float(f.ms_parse)
+        self._index = None
+
+    def seq_index(self) -> SeqIndex:
+        """The sequence index of the records (their buffers are the library's
+        and never change), created on first use."""
+        if self._index is None:
+            self._index = SeqIndex(self.struct())
+        return self._index
 
     @property
     def nseq(self) -> int:
@@ -278,6 +339,9 @@ class FastaSeqs:
         return [b[int(a):int(e)] for a, e in zip(self.offsets[:-1], self.offsets[1:])]
 
     def close(self):
+        if self._index is not None:
+            self._index.close()
+            self._index = None
         if self._f is not None:
             load().ks_fasta_free(C.byref(self._f))
             self._f = None

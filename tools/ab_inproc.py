@@ -28,6 +28,13 @@ def main():
     p.add_argument("--scale", type=float, default=1.0)
     p.add_argument("--ncontigs", type=int, default=24)
     p.add_argument("--out", default=None)
+    p.add_argument("--warmup-rounds", type=int, default=0,
+                   help="run this many rounds first and leave them out of every statistic (the first round pays "
+                        "first-touch allocations and clock ramp-up)")
+    p.add_argument("--discard", type=int, default=0,
+                   help="leave the first N steps of every variant's round out of the statistics (a variant whose "
+                        "first step after another variant's differs by design: KS_NO_SEQ_INDEX=1 before a sequence "
+                        "index variant makes that variant's first step a build)")
     p.add_argument("--shard-of", type=int, default=1,
                    help="scan only the largest of N LPT shards (the whole genome's count and table)")
     p.add_argument("--rebuild", action="store_true",
@@ -75,10 +82,12 @@ def main():
         ds = ds.subset(sorted(mine))
         print("shard", a.shard_of, "contigs", sorted(mine), "bp", int(ds.total), flush=True)
     res = {n: [] for n, _ in variants}
+    rounds = {n: [] for n, _ in variants}  # per-round median step
+    runs_ms = {n: [] for n, _ in variants}  # ms_runs of every kept step
     phases = {}
     ref = None
-    for r in range(a.rounds):
-        if a.rebuild and r:
+    for r in range(-a.warmup_rounds, a.rounds):
+        if a.rebuild and r > -a.warmup_rounds:
             tab.close()
             torch.cuda.synchronize()
             tab = D.DeviceTable.from_counts(ctx, counts, a.k, a.score, total=words, thr=thr, expand=True)
@@ -86,14 +95,18 @@ def main():
             old = {key: os.environ.get(key) for key in env}
             os.environ.update(env)
             try:
-                for _ in range(a.steps):
+                kept = []
+                for i_step in range(a.steps + a.discard):
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     pos, sc, st = D.scan(ctx, ds, a.k, tabs.get(name, tab), 100, 20.0)
                     torch.cuda.synchronize()
                     ms = (time.perf_counter() - t0) * 1e3
-                    res[name].append(ms)
-                    if ms <= min(res[name]):
+                    if i_step >= a.discard and r >= 0:
+                        res[name].append(ms)
+                        kept.append(ms)
+                        runs_ms[name].append(st["ms_runs"])
+                    if i_step >= a.discard and r >= 0 and ms <= min(res[name]):
                         phases[name] = {key: round(st[key], 3) for key in
                                         ("ms_runs", "ms_layout", "ms_scan", "ms_predict", "ms_carry", "ms_stitch",
                                          "ms_rescan", "ms_finish")}
@@ -101,17 +114,23 @@ def main():
                         ref = (pos.copy(), np.ascontiguousarray(sc).copy())
                     elif not (np.array_equal(pos, ref[0]) and np.array_equal(sc, ref[1])):
                         raise SystemExit(f"variant {name}: regions differ from the first variant's")
+                if r >= 0:
+                    rounds[name].append(statistics.median(kept))
             finally:
                 for key, v in old.items():
                     if v is None:
                         os.environ.pop(key, None)
                     else:
                         os.environ[key] = v
-        print(f"round {r}: " + "  ".join(f"{n} {min(res[n][-a.steps:]):.3f}" for n, _ in variants), flush=True)
+        if r >= 0:
+            print(f"round {r}: " + "  ".join(f"{n} {min(res[n][-a.steps:]):.3f}" for n, _ in variants), flush=True)
     out = {}
     for name, env in variants:
         v = res[name]
         out[name] = {"env": env, "min_ms": round(min(v), 3), "median_ms": round(statistics.median(v), 3),
+                     "round_medians_ms": [round(x, 3) for x in rounds[name]],
+                     "round_median_spread_ms": round(max(rounds[name]) - min(rounds[name]), 3),
+                     "median_ms_runs": round(statistics.median(runs_ms[name]), 3),
                      "best_phases": phases[name]}
         print(name, json.dumps(out[name]))
     if a.out:
