@@ -736,6 +736,105 @@ ks_status ks_hclust(ks_ctx *ctx, const double *diss, int64_t n, int32_t method, 
  * linkage h bounds every group's diameter. */
 ks_status ks_hclust_cut(const int32_t *merge, const double *height, int64_t n, int32_t k, double h, int32_t *group);
 
+/* ---------------------------------------------------------------------
+ * Neighbour-joining tree of a condensed dissimilarity vector
+ * (csrc/ks_nj.hip).
+ * --------------------------------------------------------------------- */
+
+/* The tree the reference's author wanted of the region distances and left
+ * commented out as "way too slow" on the host (ape's nj, test.R:770-775,
+ * :861-864) -- without taking the matrix to the host.
+ *
+ * Input: a condensed dissimilarity vector as ks_spectra_dist_dev writes it,
+ * n (n - 1) / 2 doubles, pair i < j at i * n - i (i + 1) / 2 + (j - i - 1)
+ * (64-bit offsets).  n >= 3.  Every entry must be finite, checked as for
+ * ks_hclust_dev and with its error text: KS_ERR_ARG, "dissimilarity at offset
+ * o is not finite", o the first such offset, before anything is modified;
+ * after a rejected call the input is untouched and the context usable.
+ *
+ * Algorithm: canonical neighbour joining (Saitou & Nei; Studier & Keppler's
+ * criterion), fixed here in 0-based terms so that a short host loop reproduces
+ * it exactly.  All arithmetic is separate FP64 operations (no FMA).
+ * State: live[i] (all true), r = n, node[i] = -(i + 1), the matrix D(i, j),
+ * and S[i] = the sum of D(i, j) over j != i, summed with j ascending in one
+ * accumulator started at +0.0.  While r > 3, step s = 0, 1, ...:
+ *   1. over the live pairs i < j in lexicographic order
+ *        q = ((double)(r - 2) * D(i, j) - S[i]) - S[j];
+ *      the smallest q wins with a strict <, so the lowest (i, j) wins a tie
+ *      (-0.0 and +0.0 compare equal: the pair decides).  If no pair has
+ *      q < +inf (the sums overflowed) the call fails with KS_ERR_ARG;
+ *   2. a = i, b = j, dab = D(a, b);
+ *        delta = (S[a] - S[b]) / (double)(r - 2);
+ *        la = 0.5 * (dab + delta);  lb = 0.5 * (dab - delta);
+ *   3. join[s] = (node[a], node[b]), length[s] = (la, lb);
+ *   4. for every live k other than a and b, with the old values of D:
+ *        dn = 0.5 * ((D(a, k) + D(b, k)) - dab);
+ *        S[k] = ((S[k] - D(a, k)) - D(b, k)) + dn;
+ *        D(a, k) = dn;
+ *   5. S[a] = 0.5 * ((S[a] + S[b]) - (double)r * dab), with the old values of
+ *      S: in exact arithmetic the sum of the new row, so nothing is summed;
+ *   6. live[b] = false, node[a] = s + 1, r = r - 1.
+ * At the end the three live rows x < y < z give
+ *   root = (node[x], node[y], node[z]),
+ *   root_length = (0.5 * ((D(x,y) + D(x,z)) - D(y,z)),
+ *                  0.5 * ((D(x,y) + D(y,z)) - D(x,z)),
+ *                  0.5 * ((D(x,z) + D(y,z)) - D(x,y))).
+ * Negative lengths are returned as computed.  n = 3 has no join.
+ * S is updated incrementally (steps 4 and 5) where ape's nj recomputes the row
+ * sums at every step: last bits, and with them the choice among near-ties,
+ * may differ from ape's.  The tree is a function of the input alone: the
+ * implementation may drop dead rows and columns from the stored matrix as
+ * long as the order of the live rows is kept, which changes no comparison and
+ * no operand.
+ *
+ * Outputs (host pointers), coded as merge of ks_hclust: observation i
+ * (0-based) appears as -(i + 1), the node made at step t (0-based) as t + 1.
+ *   join        [n - 3][2] int32, row-major, in step order
+ *   length      [n - 3][2] double: the edges from the step's node to the two
+ *   root        [3] int32: the children of the final trifurcation
+ *   root_length [3] double */
+#define KS_NJ_KEEP_INPUT 1 /* flags: join a device copy, leave diss_dev untouched */
+#define KS_NJ_NO_COMPACT 2 /* flags: never compact the matrix (same tree; for measurements) */
+typedef struct ks_nj_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total; /* first check launch to the end of the last kernel */
+  double ms_check; /* the finiteness pass */
+  double ms_init;  /* the KEEP_INPUT copy, if any, and the row sums */
+  double ms_join;  /* the n - 3 steps, compactions included, and the root */
+  int64_t n;
+  int64_t n_compactions; /* times the live rows were copied to a smaller matrix */
+  int64_t work_bytes;    /* device memory the call allocated and freed: the KEEP_INPUT copy and the compaction buffer */
+} ks_nj_stats;
+
+/* diss_dev is a device pointer.  Without KS_NJ_KEEP_INPUT it is OVERWRITTEN;
+ * with the flag the call allocates a copy (KS_ERR_NOMEM if it cannot) and the
+ * input's bits are unchanged afterwards.  Compaction: whenever a join leaves
+ * r <= m / 2 live rows of the m stored ones (and r >= 8) the live rows are
+ * copied, in order, to a matrix of r rows; the copies alternate between the
+ * matrix and one buffer of (n / 2)(n / 2 - 1) / 2 doubles, under a quarter of
+ * the matrix, allocated when n >= 16 and counted in work_bytes.  The O(n)
+ * state (53 n bytes + 32 KiB) comes from the context workspace and is not
+ * counted.  All arguments are validated before any device call (n < 3,
+ * unknown flag bits, null pointers).  stats may be NULL.  ctx == NULL is the
+ * default context on device 0; the calls are never spread over a device list
+ * and are not forwarded by the fork broker. */
+ks_status ks_nj_dev(ks_ctx *ctx, double *diss_dev, int64_t n, int32_t flags, int32_t *join, double *length,
+                    int32_t *root, double *root_length, ks_nj_stats *stats);
+/* Host buffers: validates every argument and every entry before any device
+ * call, then uploads and runs the device entry on the upload. */
+ks_status ks_nj(ks_ctx *ctx, const double *diss, int64_t n, int32_t *join, double *length, int32_t *root,
+                double *root_length);
+/* The tree as an edge table: host only, no context, O(n).  The layout of
+ * ape's phylo object (what the author converts trees to, test.R:824): tips
+ * 1 .. n, the trifurcation n + 1, the node of step t as 2n - 2 - t (so
+ * n - 2 internal nodes n + 1 .. 2n - 2); edge [2n - 3][2] int32 (parent,
+ * child) and edge_length [2n - 3], in preorder from the trifurcation with
+ * children in stored order.  join and length may be NULL when n = 3.
+ * KS_ERR_ARG for a malformed table: a code that is neither an observation nor
+ * (in join[t]) an earlier step, or a node used twice -- a table that leaves a
+ * node out uses another twice. */
+ks_status ks_nj_edges(const int32_t *join, const double *length, const int32_t *root, const double *root_length,
+                      int64_t n, int32_t *edge, double *edge_length);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

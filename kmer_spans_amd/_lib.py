@@ -91,6 +91,14 @@ class HclustStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class NjStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_init", C.c_double),
+                ("ms_join", C.c_double), ("n", C.c_int64), ("n_compactions", C.c_int64), ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -126,6 +134,7 @@ EXPORTS = [
     "ks_spectra_dist", "ks_spectra_dist_dev", "ks_spectra_cross_dist", "ks_spectra_cross_dist_dev",
     "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
     "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
+    "ks_nj", "ks_nj_dev", "ks_nj_edges",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
 ]
@@ -136,6 +145,8 @@ KS_DIST_MAX_NCOL = 4096
 KS_DIST_SQUARED = 1
 HCLUST_METHODS = {"complete": 0, "single": 1, "average": 2}  # KS_HCLUST_*
 KS_HCLUST_KEEP_INPUT = 1
+KS_NJ_KEEP_INPUT = 1
+KS_NJ_NO_COMPACT = 2
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -214,6 +225,9 @@ def load():
         "ks_hclust": ([P, P, I64, I32, P, P, P], I32),
         "ks_hclust_dev": ([P, P, I64, I32, I32, P, P, P, P], I32),
         "ks_hclust_cut": ([P, P, I64, I32, D, P], I32),
+        "ks_nj": ([P, P, I64, P, P, P, P], I32),
+        "ks_nj_dev": ([P, P, I64, I32, P, P, P, P, P], I32),
+        "ks_nj_edges": ([P, P, P, P, I64, P, P], I32),
         "ks_seq_index_create": ([P, P], I32),
         "ks_seq_index_destroy": ([P], None),
         "ks_seq_index_info_get": ([P, P], I32),
@@ -366,3 +380,17 @@ def hclust_method(method) -> int:
 
 def hclust_outputs(n: int):
     return np.zeros((n - 1, 2), dtype=np.int32), np.zeros(n - 1, dtype=np.float64), np.zeros(n, dtype=np.int32)
+
+
+def nj_n(length: int) -> int:
+    """n of a condensed vector of n(n-1)/2 entries (n >= 3), or an error."""
+    n = (1 + int(np.sqrt(1.0 + 8.0 * length))) // 2
+    for m in (n - 1, n, n + 1):
+        if m >= 3 and m * (m - 1) // 2 == length:
+            return m
+    raise KmerSpansError(f"a condensed vector holds n(n-1)/2 entries for some n >= 3; {length} is no such number")
+
+
+def nj_outputs(n: int):
+    return (np.zeros((n - 3, 2), dtype=np.int32), np.zeros((n - 3, 2), dtype=np.float64),
+            np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.float64))

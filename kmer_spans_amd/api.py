@@ -339,6 +339,96 @@ def cut_tree(tree_or_merge, height=None, k=None, h=None) -> np.ndarray:
     return group
 
 
+def region_nj(dist, device: int = 0) -> dict:
+    """ape's nj() of a condensed dissimilarity vector (the tree test.R:770-775
+    and :861-864 give up on as far too slow), run on the device.
+
+    dist: float64[n(n-1)/2], the condensed form region_distances returns; n >=
+    3 is solved from its length.  Every entry must be finite.  Canonical
+    neighbour joining with every tie going to the lowest pair and the row sums
+    updated incrementally (include/kmer_spans.h has the order of operations;
+    last bits may differ from ape's, which recomputes the sums).  Returns
+    {'join': int32[n-3, 2], 'length': float64[n-3, 2], 'root': int32[3],
+    'root_length': float64[3]}: step t joins the nodes join[t] by edges of
+    length[t] into node t+1, observation i (0-based) is -(i+1), and root names
+    the three children of the final trifurcation.  Negative lengths are
+    returned as computed."""
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    if d.ndim != 1:
+        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
+    n = _lib.nj_n(int(d.size))
+    join, length, root, root_length = _lib.nj_outputs(n)
+    check(load().ks_nj(_ctx(device), d.ctypes.data, n, join.ctypes.data, length.ctypes.data, root.ctypes.data,
+                       root_length.ctypes.data))
+    return {"join": join, "length": length, "root": root, "root_length": root_length}
+
+
+def _nj_tables(tree):
+    """(join, length, root, root_length, n) of a region_nj tree, shapes checked."""
+    join = np.ascontiguousarray(tree["join"], dtype=np.int32)
+    length = np.ascontiguousarray(tree["length"], dtype=np.float64)
+    root = np.ascontiguousarray(tree["root"], dtype=np.int32)
+    root_length = np.ascontiguousarray(tree["root_length"], dtype=np.float64)
+    if (join.ndim != 2 or join.shape[1] != 2 or length.shape != join.shape or root.shape != (3,)
+            or root_length.shape != (3,)):
+        raise KmerSpansError("a tree holds join and length [n-3, 2], root and root_length [3]")
+    return join, length, root, root_length, int(join.shape[0]) + 3
+
+
+def nj_edges(tree) -> dict:
+    """The tree of region_nj in the layout of ape's phylo object (test.R:824),
+    on the host: tips 1 .. n, the trifurcation n+1, the node of step t as
+    2n-2-t.  Returns {'edge': int32[2n-3, 2] (parent, child), 'edge_length':
+    float64[2n-3], 'Nnode': n-2, 'n_tip': n}, in preorder from the
+    trifurcation with children in stored order."""
+    join, length, root, root_length, n = _nj_tables(tree)
+    edge = np.zeros((2 * n - 3, 2), dtype=np.int32)
+    edge_length = np.zeros(2 * n - 3, dtype=np.float64)
+    check(load().ks_nj_edges(join.ctypes.data if n > 3 else None, length.ctypes.data if n > 3 else None,
+                             root.ctypes.data, root_length.ctypes.data, n, edge.ctypes.data,
+                             edge_length.ctypes.data))
+    return {"edge": edge, "edge_length": edge_length, "Nnode": n - 2, "n_tip": n}
+
+
+def nj_newick(tree, labels=None) -> str:
+    """The tree of region_nj as a Newick string, '(a:1.0,(b:0.5,c:0.25):2.0,d:1.5);'.
+    Lengths are written with repr(), so they read back as the same doubles.
+    labels: n strings without Newick punctuation (default '1' .. 'n')."""
+    join, length, root, root_length, n = _nj_tables(tree)
+    if labels is None:
+        labels = [str(i + 1) for i in range(n)]
+    labels = [str(x) for x in labels]
+    if len(labels) != n:
+        raise KmerSpansError(f"{n} labels are needed, {len(labels)} were given")
+    for x in labels:
+        if not x or any(c in x for c in "():,; \t\n'[]"):
+            raise KmerSpansError(f"label {x!r} is empty or holds Newick punctuation")
+    nj_edges(tree)  # rejects a malformed table, so the walk below ends
+    # an explicit stack (a caterpillar tree is n deep): strings are emitted as
+    # they are, (code, length) pairs are expanded
+    out = []
+    stack = [";", ")"]
+    for c in (2, 1, 0):
+        stack.append((int(root[c]), float(root_length[c])))
+        stack.append("," if c else "(")
+    while stack:
+        item = stack.pop()
+        if isinstance(item, str):
+            out.append(item)
+            continue
+        code, ln = item
+        if code < 0:
+            out.append(f"{labels[-code - 1]}:{ln!r}")
+        else:
+            t = code - 1
+            stack.append(f"):{ln!r}")
+            stack.append((int(join[t, 1]), float(length[t, 1])))
+            stack.append(",")
+            stack.append((int(join[t, 0]), float(length[t, 0])))
+            stack.append("(")
+    return "".join(out)
+
+
 # ------------------------------------------------------------ table builders
 
 def _table(fn, counts, k):

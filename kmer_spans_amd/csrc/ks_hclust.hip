@@ -13,10 +13,10 @@
 // bits; average linkage is two multiplications, an addition and a division as
 // separate FP64 operations (-ffp-contract=off, csrc/Makefile).
 //
-// Check:  k_hclust_check reads the matrix once (16-byte loads, grid-stride)
-//         and keeps the lowest offset of a non-finite entry (atomicMin); one
-//         8-byte read-back ends a call with a bad entry before anything is
-//         modified.
+// Check:  k_hclust_check (ks_finite_check.h, shared with ks_nj.hip) reads the
+//         matrix once (16-byte loads, grid-stride) and keeps the lowest offset
+//         of a non-finite entry (atomicMin); one 8-byte read-back ends a call
+//         with a bad entry before anything is modified.
 // Init:   k_hclust_init: a block of 256 threads per row i scans the contiguous
 //         segment D(i, i+1 .. n-1) for (min, lowest j).
 // Merge:  two launches per step, 2 (n - 1) in all, queued on the stream with no
@@ -46,6 +46,7 @@
 #include "ks_internal.h"
 // after hip_runtime.h (ks_internal.h): the header's functions are __host__ __device__ here
 #include "ks_dist_index.h"
+#include "ks_finite_check.h"
 
 namespace ks {
 namespace {
@@ -57,7 +58,6 @@ constexpr int kHcPairRows = 4096; // k_hclust_pair: a block per so many k of the
 constexpr int kHcPairBlocks = 8;  //   at most so many (each block repeats the arg-min)
 constexpr int kHcRescanBlocks = 16;  // k_hclust_rescan: rows rescanned side by side
 constexpr int kNone = 0x7fffffff; // "no index": loses every tie, equals no row
-constexpr unsigned long long kNoBad = ~0ULL;
 
 // (value, index) ordering of every reduction here: the smaller value, the
 // lower index on equal values (-0.0 == +0.0: the index decides).
@@ -84,31 +84,6 @@ __device__ __forceinline__ void hc_block_min(double &v, int &i, double *sv, int 
   hc_wave_min(v, i, kHcWaves);
   v = __shfl(v, 0);
   i = __shfl(i, 0);
-}
-
-__global__ void __launch_bounds__(256) k_hclust_check(const double *__restrict__ d, int64_t total,
-                                                      unsigned long long *__restrict__ bad) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t pairs2 = total >> 1;  // hipMalloc'd or offset by whole tensors: checked for 16-byte alignment by the caller
-  unsigned long long first = kNoBad;
-  const double2 *d2 = reinterpret_cast<const double2 *>(d);
-  for (int64_t p = t0; p < pairs2; p += stride) {
-    const double2 x = d2[p];
-    // ascending p per thread: the first hit is this thread's lowest
-    if (first == kNoBad && !(isfinite(x.x) && isfinite(x.y))) first = (unsigned long long)(2 * p + (isfinite(x.x) ? 1 : 0));
-  }
-  if (t0 == 0 && (total & 1) && !isfinite(d[total - 1]) && first == kNoBad) first = (unsigned long long)(total - 1);
-  if (first != kNoBad) atomicMin(bad, first);
-}
-
-// the same for a base address that is only 8-byte aligned
-__global__ void __launch_bounds__(256) k_hclust_check1(const double *__restrict__ d, int64_t total,
-                                                       unsigned long long *__restrict__ bad) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  unsigned long long first = kNoBad;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride)
-    if (first == kNoBad && !isfinite(d[p])) first = (unsigned long long)p;
-  if (first != kNoBad) atomicMin(bad, first);
 }
 
 // The O(n) state of a call, one allocation (HcState::bytes).
@@ -326,10 +301,6 @@ ks_status check_hclust_args(int64_t n, int32_t method, int32_t flags, const void
   return KS_OK;
 }
 
-ks_status not_finite(unsigned long long off) {
-  return fail(KS_ERR_ARG, "dissimilarity at offset %llu is not finite", off);
-}
-
 // Everything validated; diss is a device pointer.
 ks_status hclust_impl(ks_ctx *ctx, double *diss, int64_t n, int method, int flags, int32_t *merge, double *height,
                       int32_t *order, ks_hclust_stats *stats) {
@@ -341,23 +312,7 @@ ks_status hclust_impl(ks_ctx *ctx, double *diss, int64_t n, int method, int flag
   unsigned long long *bad = static_cast<unsigned long long *>(scal) + kScHclustBad;
 
   // every entry is checked before anything is modified
-  KS_HIP(hipEventRecord(ctx->ev[0], st));
-  unsigned long long hbad = kNoBad;
-  KS_HIP(hipMemsetAsync(bad, 0xff, 8, st));
-  {
-    const bool al16 = (reinterpret_cast<uintptr_t>(diss) & 15) == 0;
-    const int64_t items = al16 ? (total + 1) / 2 : total;
-    const unsigned grid = (unsigned)std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cus * 8);
-    if (al16)
-      hipLaunchKernelGGL(k_hclust_check, dim3(grid), dim3(256), 0, st, diss, total, bad);
-    else
-      hipLaunchKernelGGL(k_hclust_check1, dim3(grid), dim3(256), 0, st, diss, total, bad);
-    KS_HIP(hipGetLastError());
-  }
-  KS_HIP(hipEventRecord(ctx->ev[1], st));
-  KS_HIP(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, st));
-  KS_HIP(hipStreamSynchronize(st));
-  if (hbad != kNoBad) return not_finite(hbad);
+  KS_TRY(check_all_finite(ctx, diss, total, bad));
 
   DevFree copy;
   double *d = diss;

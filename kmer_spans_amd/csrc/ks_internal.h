@@ -82,7 +82,8 @@ constexpr int kScSumWords = 96;    // count_words: sum of a histogram
 constexpr int kScMultiWords = 104; // launch_count_multi: words per k of a batch [104, 112)
 constexpr int kScDistBad = 112;    // dist_impl: first bad row index of each selection [112, 114)
 constexpr int kScHclustBad = 114;  // hclust_impl: lowest offset of a non-finite dissimilarity
-constexpr int kScEnd = 115;
+constexpr int kScNjBad = 115;      // nj_impl: the same
+constexpr int kScEnd = 116;
 
 struct DevBuf {
   void *ptr = nullptr;

@@ -541,3 +541,30 @@ def region_hclust(ctx: _lib.Context, dist: torch.Tensor, method: str = "complete
                                _lib.hclust_method(method), _lib.KS_HCLUST_KEEP_INPUT if keep_input else 0,
                                merge.ctypes.data, height.ctypes.data, order.ctypes.data, C.byref(st)))
     return {"merge": merge, "height": height, "order": order, "method": method}, st.as_dict()
+
+
+def region_nj(ctx: _lib.Context, dist: torch.Tensor, keep_input: bool = True, compact: bool = True):
+    """ks_nj_dev: the neighbour-joining tree (ape's nj, test.R:770-775) of the
+    condensed distances region_distances returns, on the device.
+
+    dist: a contiguous float64 CUDA tensor of n(n-1)/2 entries, n >= 3, every
+    entry finite (a NaN from an empty spectrum row is an error naming its
+    offset; the tensor is untouched then).  keep_input=True joins a device copy
+    and leaves dist's bits unchanged; keep_input=False updates dist in place
+    and consumes it.  compact=False keeps the matrix at n rows throughout (the
+    same tree; for measurements).  Returns (tree, stats): tree is a dict of
+    join int32 [n-3, 2], length float64 [n-3, 2], root int32 [3] and
+    root_length float64 [3] (numpy; observation i is -(i+1), the node of step t
+    is t+1); stats the dict of ks_nj_stats."""
+    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
+            or not dist.is_contiguous()):
+        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
+    n = _lib.nj_n(int(dist.numel()))
+    join, length, root, root_length = _lib.nj_outputs(n)
+    st = _lib.NjStats()
+    flags = (_lib.KS_NJ_KEEP_INPUT if keep_input else 0) | (0 if compact else _lib.KS_NJ_NO_COMPACT)
+    _order(ctx)
+    check(load().ks_nj_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n, flags,
+                           join.ctypes.data, length.ctypes.data, root.ctypes.data, root_length.ctypes.data,
+                           C.byref(st)))
+    return {"join": join, "length": length, "root": root, "root_length": root_length}, st.as_dict()
