@@ -795,6 +795,185 @@ __global__ void __launch_bounds__(1024) k_predict(Chunks g, int64_t total, int k
 
 // ------------------------------------------------------------------- P1
 
+// Every pass-1 kernel does the same work per scan index of a chunk and differs
+// only in how it fetches the value s: that work is P1Lane below (init / step /
+// finish), used by k_pass1l, k_pass1w, k_pass1r, k_pass1pf and k_pass1_lds.
+// Three kernels keep a walk of their own.  k_pass1_lds_int walks on int32:
+// 32-bit integer compares instead of FP64 ones are the point of that kernel.
+// k_pass1p keeps a copy in locals, for its registers (see there).  k_pass1
+// keeps its if / else-if form that asks decide(): on the walker its J = 1
+// instantiations took 147-161 VGPRs instead of 181-191 and ran slower (see
+// there).  All share the candidate append (cand_put) and the result store
+// (p1_put).  So the emission rule (the candidate test) is written in four
+// places: P1Lane::step, k_pass1p, for kmer_regions alone k_pass1_lds_int, and
+// decide(), which k_pass1 (cand_wanted), the stitch and k_candidates ask.
+
+// A closed candidate excursion of the chunk starting at scan index start
+// (chunk-relative beg, arg, end) joins the segmented list.
+__device__ __forceinline__ void cand_put(const Cand &cand, int64_t start, int beg, int arg, int end, double best) {
+  const int64_t slot = append_one(cand.count, cand.segcap);
+  if (slot >= 0) {
+    cand.beg[slot] = start + beg;
+    cand.arg[slot] = start + arg;
+    cand.rst[slot] = start + end;
+    cand.best[slot] = best;
+  }
+}
+
+// Chunk c's pass-1 results, stamped with the call's epoch: the aggregates,
+// the clean exit prev and the trailing open excursion (beg, best, arg) if any.
+__device__ __forceinline__ void p1_put(const P1 &o, int64_t c, double prev, double asum, double pmin, double pmax,
+                                       int parg, double sabs, bool special, int beg, double best, int arg) {
+  o.cexit[c] = prev;
+  o.asum[c] = asum;
+  o.pmin[c] = pmin;
+  o.pmax[c] = pmax;
+  o.parg[c] = parg;
+  o.sabs[c] = sabs;
+  o.special[c] = special ? 1 : 0;
+  o.ep[c] = o.epoch;
+  if (prev > 0) {
+    o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
+  } else {
+    o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
+  }
+}
+
+// Per-lane state of pass 1 over one chunk: the clean-entry trajectory, its
+// aggregates, closed candidates and (kSumm) the binade-integer summaries in
+// the predicted binade and its neighbour.
+//
+// The summary of this chunk for the binade of its predicted entry xp
+// (k_predict), single trajectory: s rounded to the binade's ulp u = 2^(e-52)
+// as (s + C) - C with C = 1.5 * 2^e, exact partial sums while they stay within
+// (-2^e, 2^e); an exact half (tie: the increment would depend on the parity of
+// the entry) or |s| >= 2^(e-1) voids it (summ_put; k_summ_fixw then recomputes
+// it).  Replaces the per-position code store and k_summaries.
+//
+// step() gives the same bits as fmin / fmax, an if / else-if chain and decide():
+// asum starts at +0, so is never -0, and a NaN asum fails both compares, as fmin
+// / fmax skip it; S > best is false at a close and while S stays 0 (best > 0
+// inside, >= 0 outside), so open | (S > best) is the chain; want is decide()'s
+// reg || res less start on both sides (pos_of: only a run's index 0 stays put).
+template <bool kSumm, bool kTrlr>
+struct P1Lane {
+  int64_t start;
+  int n, f0;
+  double prev = 0.0, best = 0.0;
+  int beg = -1, arg = 0;
+  double asum = 0.0, pmin = INFINITY, pmax = -INFINITY, sabs = 0.0;
+  int parg = 0;
+  bool special = false;
+  int se = INT32_MIN, se2 = INT32_MIN;
+  double sC = 0.0, sH = 0.0, scur = 0.0, smx = -INFINITY, smn = INFINITY;
+  double sC2 = 0.0, sH2 = 0.0, scur2 = 0.0, smx2 = -INFINITY, smn2 = INFINITY;
+  double smaxabs = 0.0;  // max |s| (the rounding of every step, both binades)
+  int sarg = 0, sarg2 = 0;
+  bool sbad = false, sbad2 = false;
+
+  // first: the chunk starts its run; xp: the predicted entry (0: no summaries)
+  __device__ __forceinline__ void init(int64_t st, int nn, bool first, bool live, double xp) {
+    start = st;
+    n = nn;
+    f0 = first ? 0 : -1;
+    if (kSumm && live && xp >= kP1SumMin && xp < 1.0e15) {
+      se = binade_of(xp);
+      sC = 1.5 * ldexp(1.0, se);
+      sH = ldexp(1.0, se - 53);
+      const double lo = ldexp(1.0, se);
+      if (xp < lo * (1.0 + kP1Margin)) se2 = se - 1;
+      else if (xp > 2.0 * lo * (1.0 - kP1Margin)) se2 = se + 1;
+      if (se2 != INT32_MIN) {
+        sC2 = 1.5 * ldexp(1.0, se2);
+        sH2 = ldexp(1.0, se2 - 53);
+      }
+    }
+  }
+
+  // scan index i (< n) with value s
+  __device__ __forceinline__ void step(double s, int i, const EmitCfg &ec, const Cand &cand) {
+    asum += s;
+    pmin = asum < pmin ? asum : pmin;
+    parg = asum > pmax ? i : parg;
+    pmax = asum > pmax ? asum : pmax;
+    sabs += fabs(s);
+    special |= !isfinite(s);
+    if (kSumm && se != INT32_MIN) {
+      const double r = (s + sC) - sC;
+      sbad |= fabs(r - s) == sH;
+      smaxabs = fmax(smaxabs, fabs(s));
+      scur += r;
+      const bool su = scur > smx;
+      smx = su ? scur : smx;
+      sarg = su ? i : sarg;
+      smn = fmin(smn, scur);
+      if (se2 != INT32_MIN) {
+        const double r2 = (s + sC2) - sC2;
+        sbad2 |= fabs(r2 - s) == sH2;
+        scur2 += r2;
+        const bool su2 = scur2 > smx2;
+        smx2 = su2 ? scur2 : smx2;
+        sarg2 = su2 ? i : sarg2;
+        smn2 = fmin(smn2, scur2);
+      }
+    }
+    // clean trajectory, branch-free except for the rare candidate: open
+    // (0 -> S > 0) starts an excursion, close (> 0 -> 0) ends it, the first
+    // strict maximum is kept
+    const double tt = prev + s;
+    const double S = tt > 0 ? tt : 0.0;
+    const bool open = (prev == 0) & (S > 0);
+    const bool close = (prev > 0) & (S == 0);
+    const long long ml = kTrlr ? ec.min_len : 0;
+    const bool want =
+        kTrlr ? (close & (((long long)((arg != f0 ? arg - 1 : arg) - (beg != f0 ? beg - 1 : beg)) >= ml) |
+                          ((long long)((i != f0 ? i - 1 : i) - (arg != f0 ? arg - 1 : arg) - 1) >=
+                           (ml > 1 ? ml : 1LL))))
+              : (close & ((uint64_t)(int64_t)(arg - beg) >= ec.mw) & (best >= ec.min_score));
+    if (want) cand_put(cand, start, beg, arg, i, best);
+    const bool up = open | (S > best);
+    best = up ? S : best;
+    arg = up ? i : arg;
+    beg = open ? i : (close ? -1 : beg);
+    prev = S;
+  }
+
+  __device__ __forceinline__ void finish(int64_t c, const P1 &o, const SummP1 &sp) {
+    if (kSumm) {
+      summ_put(sp, c, 0, se, sbad, smaxabs, scur, smx, smn, sarg);
+      summ_put(sp, c, 1, se2, sbad2, smaxabs, scur2, smx2, smn2, sarg2);
+    }
+    p1_put(o, c, prev, asum, pmin, pmax, parg, sabs, special, beg, best, arg);
+  }
+};
+
+// The packed window of the small-k passes, 16 scan indices per batch: their
+// k-mers (k <= 16) from one 64-bit window of packed bases, three words loaded
+// one batch ahead (words past the last one, total >> 4, read it again).
+struct Window16 {
+  const uint32_t *__restrict__ packed;
+  int64_t last;
+  uint3 cur;
+
+  __device__ __forceinline__ uint3 load3(int64_t q) const {
+    const int64_t w = q >> 4;
+    return make_uint3(packed[min(w, last)], packed[min(w + 1, last)], packed[min(w + 2, last)]);
+  }
+  __device__ __forceinline__ Window16(const uint32_t *__restrict__ pk, int64_t total, int64_t q0)
+      : packed(pk), last(total >> 4) {
+    cur = load3(q0);
+  }
+  // the 32 bases from q on, first base most significant; q + 16 comes next
+  __device__ __forceinline__ uint64_t take(int64_t q) {
+    const uint3 nxt = load3(q + 16);
+    const uint32_t bp = 2u * (uint32_t)(q & 15);
+    const uint64_t x = ((((uint64_t)cur.x << 32) | cur.y) << bp) | (((uint64_t)cur.z << bp) >> 32);
+    cur = nxt;
+    return x;
+  }
+};
+
+
 // A closed excursion of a chunk's clean trajectory (chunk-relative beg, arg,
 // end) is kept as a candidate if it could emit a region or (tr_lr) needs a
 // rescan; first = the chunk starts its run.
@@ -805,12 +984,15 @@ __device__ __forceinline__ bool cand_wanted(const EmitCfg &ec, bool first, int64
   return e.reg || e.res;
 }
 
-
 // J = scan indices served by one table read: 1 reads the base table
 // (uint16 code or FP64 value per index); J >= 2 reads the expanded table
 // entry of the (k+J-1)-mer that spans J consecutive indices.
 // kLds: the compressed LUT is copied to LDS once per 1024-lane block
 // (random LUT reads hit LDS banks instead of the L1/L2 path).
+// The per-index step is hand-written here, not P1Lane's (same bits, see the
+// comment there): on the walker k_pass1<1, *> went from 181 / 191 VGPRs and 2
+// waves per SIMD to 147-161 and 3, and the unexpanded k = 13 scan of 3.09 Gbp
+// took 89.0 instead of 87.5 ms per step.
 template <int J, bool kCompressed, bool kLds>
 __global__ void __launch_bounds__(J == 1 ? 256 : 1024) k_pass1(Chunks g, const uint8_t *__restrict__ seq, int64_t total,
                                                 int k, TableView tv, uint16_t *__restrict__ codes,
@@ -938,15 +1120,7 @@ __global__ void __launch_bounds__(J == 1 ? 256 : 1024) k_pass1(Chunks g, const u
         if (prev == 0 && S > 0) {
           beg = i; arg = i; best = S;
         } else if (prev > 0 && S == 0) {
-          if (cand_wanted(ec, first, start, beg, arg, i, best)) {
-            const int64_t slot = append_one(cand.count, cand.segcap);
-            if (slot >= 0) {
-              cand.beg[slot] = start + beg;
-              cand.arg[slot] = start + arg;
-              cand.rst[slot] = start + i;
-              cand.best[slot] = best;
-            }
-          }
+          if (cand_wanted(ec, first, start, beg, arg, i, best)) cand_put(cand, start, beg, arg, i, best);
           beg = -1;
         } else if (S > best) {
           best = S; arg = i;
@@ -955,19 +1129,7 @@ __global__ void __launch_bounds__(J == 1 ? 256 : 1024) k_pass1(Chunks g, const u
       }
     }
   }
-  o.cexit[c] = prev;
-  o.asum[c] = asum;
-  o.pmin[c] = pmin;
-  o.pmax[c] = pmax;
-  o.parg[c] = parg;
-  o.sabs[c] = sabs;
-  o.special[c] = special ? 1 : 0;
-  o.ep[c] = o.epoch;
-  if (prev > 0) {
-    o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
-  } else {
-    o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
-  }
+  p1_put(o, c, prev, asum, pmin, pmax, parg, sabs, special, beg, best, arg);
 }
 
 // Software-pipelined gather pass for expanded compressed tables (J >= 2):
@@ -1095,15 +1257,12 @@ __global__ void __launch_bounds__(kP1Block) k_pass1p(Chunks g, const uint8_t *__
   double asum = 0.0, pmin = INFINITY, pmax = -INFINITY, sabs = 0.0;
   int parg = 0;
   bool special = false;
-  // The binade-integer summary of this chunk for the binade of its
-  // predicted entry xh (k_predict), single trajectory: s rounded to the binade's
-  // ulp u = 2^(e-52) as (s + C) - C with C = 1.5 * 2^e, exact partial sums while
-  // they stay within (-2^e, 2^e); an exact half (tie: the increment would depend
-  // on the parity of the entry) or |s| >= 2^(e-1) voids it (k_summ_fixw then
-  // recomputes it).  Replaces the per-position code store and k_summaries.
-  // (|s| < 2^(e-1) is checked once through sabs, and the minimum through the
-  // FP64 prefix minimum: N is stored as a lower bound, which keeps the carry's
-  // validity test conservative; both save registers in this 128-VGPR kernel.)
+  // A deliberate copy of P1Lane (state, init, step, finish; keep them in
+  // step): as locals the non-finite flag is a lane mask, as a member updated
+  // in place it is a byte in a VGPR, and J = 5 sits at the 128-VGPR cap of a
+  // 1024-lane block.  Scratch bytes per lane of k_pass1p<5, kLds, kTrlr> for
+  // (kLds, kTrlr) = (0, 0) (0, 1) (1, 0) (1, 1): 20 28 20 28 on the walker,
+  // 12 28 12 20 with this copy (-Rpass-analysis=kernel-resource-usage).
   int se = INT32_MIN, se2 = INT32_MIN;
   double sC = 0.0, sH = 0.0, scur = 0.0, smx = -INFINITY, smn = INFINITY;
   double sC2 = 0.0, sH2 = 0.0, scur2 = 0.0, smx2 = -INFINITY, smn2 = INFINITY;
@@ -1203,8 +1362,6 @@ __global__ void __launch_bounds__(kP1Block) k_pass1p(Chunks g, const uint8_t *__
         const int i = b0 + j;
         if (i < n) {
           if (visits) atomicAdd(&visits[(uint32_t)(gc[gi] >> (2 * (J - 1 - t))) & kmask], 1u);
-          // aggregates (selects give fmin/fmax's values: asum is never a
-          // signalling NaN and a NaN asum never replaces the extreme)
           asum += s;
           pmin = asum < pmin ? asum : pmin;
           parg = asum > pmax ? i : parg;
@@ -1230,17 +1387,10 @@ __global__ void __launch_bounds__(kP1Block) k_pass1p(Chunks g, const uint8_t *__
               smn2 = fmin(smn2, scur2);
             }
           }
-          // clean trajectory, branch-free except for the rare candidate:
-          // open (0 -> S > 0) starts an excursion, close (> 0 -> 0) ends it,
-          // the first strict maximum is kept (S > best is false at a close
-          // and while S stays 0, since best > 0 inside and >= 0 outside)
           const double tt = prev + s;
           const double S = tt > 0 ? tt : 0.0;
           const bool open = (prev == 0) & (S > 0);
           const bool close = (prev > 0) & (S == 0);
-          // kmer_regions: decide()'s region test on chunk-relative indices
-          // tr_lr: decide()'s tests on chunk-relative positions (pos_of: the
-          // run's first index keeps its position, later ones report j - 1)
           const int f0 = first ? 0 : -1;
           const long long ml = kTrlr ? ec.min_len : 0;
           const bool want =
@@ -1249,13 +1399,7 @@ __global__ void __launch_bounds__(kP1Block) k_pass1p(Chunks g, const uint8_t *__
                                  (ml > 1 ? ml : 1LL))))
                     : (close & ((uint64_t)(int64_t)(arg - beg) >= ec.mw) & (best >= ec.min_score));
           if (want) {
-            const int64_t slot = append_one(cand.count, cand.segcap);
-            if (slot >= 0) {
-              cand.beg[slot] = start + beg;
-              cand.arg[slot] = start + arg;
-              cand.rst[slot] = start + i;
-              cand.best[slot] = best;
-            }
+            cand_put(cand, start, beg, arg, i, best);
             __builtin_amdgcn_s_waitcnt(0x0F70);
           }
           const bool up = open | (S > best);
@@ -1274,19 +1418,7 @@ __global__ void __launch_bounds__(kP1Block) k_pass1p(Chunks g, const uint8_t *__
   }
   summ_put(sp, c, 0, se, sbad, smaxabs, scur, smx, smn, sarg);
   summ_put(sp, c, 1, se2, sbad2, smaxabs, scur2, smx2, smn2, sarg2);
-  o.cexit[c] = prev;
-  o.asum[c] = asum;
-  o.pmin[c] = pmin;
-  o.pmax[c] = pmax;
-  o.parg[c] = parg;
-  o.sabs[c] = sabs;
-  o.special[c] = special ? 1 : 0;
-  o.ep[c] = o.epoch;
-  if (prev > 0) {
-    o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
-  } else {
-    o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
-  }
+  p1_put(o, c, prev, asum, pmin, pmax, parg, sabs, special, beg, best, arg);
 }
 
 // ------------------------------------------------------------------- P1 (line tables)
@@ -1327,119 +1459,6 @@ __device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds) {
                : "v"(gsrc), "s"(lds)
                : "memory");
 }
-
-// Per-lane state of a line pass over one chunk: the clean-entry trajectory,
-// its aggregates, closed candidates and (kSumm) the binade-integer summaries
-// in the predicted binade and its neighbour -- the per-index work of
-// k_pass1p, shared by k_pass1l and k_pass1w.
-template <bool kSumm, bool kTrlr>
-struct P1Lane {
-  int64_t start;
-  int n, f0;
-  double prev = 0.0, best = 0.0;
-  int beg = -1, arg = 0;
-  double asum = 0.0, pmin = INFINITY, pmax = -INFINITY, sabs = 0.0;
-  int parg = 0;
-  bool special = false;
-  int se = INT32_MIN, se2 = INT32_MIN;
-  double sC = 0.0, sH = 0.0, scur = 0.0, smx = -INFINITY, smn = INFINITY;
-  double sC2 = 0.0, sH2 = 0.0, scur2 = 0.0, smx2 = -INFINITY, smn2 = INFINITY;
-  double smaxabs = 0.0;
-  int sarg = 0, sarg2 = 0;
-  bool sbad = false, sbad2 = false;
-
-  __device__ __forceinline__ void init(int64_t st, int nn, bool first, bool live, double xp) {
-    start = st;
-    n = nn;
-    f0 = first ? 0 : -1;
-    if (kSumm && live && xp >= kP1SumMin && xp < 1.0e15) {
-      se = binade_of(xp);
-      sC = 1.5 * ldexp(1.0, se);
-      sH = ldexp(1.0, se - 53);
-      const double lo = ldexp(1.0, se);
-      if (xp < lo * (1.0 + kP1Margin)) se2 = se - 1;
-      else if (xp > 2.0 * lo * (1.0 - kP1Margin)) se2 = se + 1;
-      if (se2 != INT32_MIN) {
-        sC2 = 1.5 * ldexp(1.0, se2);
-        sH2 = ldexp(1.0, se2 - 53);
-      }
-    }
-  }
-
-  // scan index i (< n) with value s
-  __device__ __forceinline__ void step(double s, int i, const EmitCfg &ec, const Cand &cand) {
-    asum += s;
-    pmin = asum < pmin ? asum : pmin;
-    parg = asum > pmax ? i : parg;
-    pmax = asum > pmax ? asum : pmax;
-    sabs += fabs(s);
-    special |= !isfinite(s);
-    if (kSumm && se != INT32_MIN) {
-      const double r = (s + sC) - sC;
-      sbad |= fabs(r - s) == sH;
-      smaxabs = fmax(smaxabs, fabs(s));
-      scur += r;
-      const bool su = scur > smx;
-      smx = su ? scur : smx;
-      sarg = su ? i : sarg;
-      smn = fmin(smn, scur);
-      if (se2 != INT32_MIN) {
-        const double r2 = (s + sC2) - sC2;
-        sbad2 |= fabs(r2 - s) == sH2;
-        scur2 += r2;
-        const bool su2 = scur2 > smx2;
-        smx2 = su2 ? scur2 : smx2;
-        sarg2 = su2 ? i : sarg2;
-        smn2 = fmin(smn2, scur2);
-      }
-    }
-    // clean trajectory (k_pass1p)
-    const double tt = prev + s;
-    const double S = tt > 0 ? tt : 0.0;
-    const bool open = (prev == 0) & (S > 0);
-    const bool close = (prev > 0) & (S == 0);
-    const long long ml = kTrlr ? ec.min_len : 0;
-    const bool want =
-        kTrlr ? (close & (((long long)((arg != f0 ? arg - 1 : arg) - (beg != f0 ? beg - 1 : beg)) >= ml) |
-                          ((long long)((i != f0 ? i - 1 : i) - (arg != f0 ? arg - 1 : arg) - 1) >=
-                           (ml > 1 ? ml : 1LL))))
-              : (close & ((uint64_t)(int64_t)(arg - beg) >= ec.mw) & (best >= ec.min_score));
-    if (want) {
-      const int64_t slot = append_one(cand.count, cand.segcap);
-      if (slot >= 0) {
-        cand.beg[slot] = start + beg;
-        cand.arg[slot] = start + arg;
-        cand.rst[slot] = start + i;
-        cand.best[slot] = best;
-      }
-    }
-    const bool up = open | (S > best);
-    best = up ? S : best;
-    arg = up ? i : arg;
-    beg = open ? i : (close ? -1 : beg);
-    prev = S;
-  }
-
-  __device__ __forceinline__ void finish(int64_t c, const P1 &o, const SummP1 &sp) {
-    if (kSumm) {  // as in k_pass1p
-      summ_put(sp, c, 0, se, sbad, smaxabs, scur, smx, smn, sarg);
-      summ_put(sp, c, 1, se2, sbad2, smaxabs, scur2, smx2, smn2, sarg2);
-    }
-    o.cexit[c] = prev;
-    o.asum[c] = asum;
-    o.pmin[c] = pmin;
-    o.pmax[c] = pmax;
-    o.parg[c] = parg;
-    o.sabs[c] = sabs;
-    o.special[c] = special ? 1 : 0;
-    o.ep[c] = o.epoch;
-    if (prev > 0) {
-      o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
-    } else {
-      o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
-    }
-  }
-};
 
 // The lane's packed 2-bit bases from the word holding base p0 on, kLineWords
 // words in registers (guarded at the end of the packed array), and a rolling
@@ -1929,24 +1948,17 @@ __global__ void __launch_bounds__(1024) k_pass1_lds_int(Chunks g, int64_t total,
   for (int i = threadIdx.x; i < nk; i += blockDim.x) s_val[i] = (int32_t)tv_get(tv, (uint32_t)i);
   __syncthreads();
   const uint32_t kmask = (uint32_t)nk - 1u;
-  const uint32_t *__restrict__ packed = g.packed;
-  const int64_t last = total >> 4;
   for (int64_t c = g.c0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < g.nch;
        c += (int64_t)gridDim.x * blockDim.x) {
     const int64_t start = g.start[c];
     const int n = g.n[c];
     const int64_t q0 = start - k;
-    auto load3 = [&](int64_t q) {
-      const int64_t w = q >> 4;
-      return make_uint3(packed[min(w, last)], packed[min(w + 1, last)], packed[min(w + 2, last)]);
-    };
-    uint3 cur = load3(q0);
+    Window16 win(g.packed, total, q0);
+    // P1Lane::step on int32 (kmer_regions only, no |s| sum, no summaries)
     int32_t prev = 0, best = 0, asum = 0, pmin = INT32_MAX, pmax = INT32_MIN;
     int beg = -1, arg = 0, parg = 0;
     for (int b0 = 0; b0 < n; b0 += 16) {
-      const uint3 nxt = load3(q0 + b0 + 16);
-      const uint32_t bp = 2u * (uint32_t)((q0 + b0) & 15);
-      const uint64_t x = ((((uint64_t)cur.x << 32) | cur.y) << bp) | (((uint64_t)cur.z << bp) >> 32);
+      const uint64_t x = win.take(q0 + b0);
       for (int j = 0; j < 16; ++j) {
         const int i = b0 + j;
         if (i >= n) break;
@@ -1962,37 +1974,48 @@ __global__ void __launch_bounds__(1024) k_pass1_lds_int(Chunks g, int64_t total,
         const bool open = (prev == 0) & (S > 0);
         const bool close = (prev > 0) & (S == 0);
         const bool want = close & ((uint64_t)(int64_t)(arg - beg) >= ec.mw) & ((double)best >= ec.min_score);
-        if (want) {
-          const int64_t slot = append_one(cand.count, cand.segcap);
-          if (slot >= 0) {
-            cand.beg[slot] = start + beg;
-            cand.arg[slot] = start + arg;
-            cand.rst[slot] = start + i;
-            cand.best[slot] = (double)best;
-          }
-        }
+        if (want) cand_put(cand, start, beg, arg, i, (double)best);
         const bool up = open | (S > best);
         best = up ? S : best;
         arg = up ? i : arg;
         beg = open ? i : (close ? -1 : beg);
         prev = S;
       }
-      cur = nxt;
     }
-    o.cexit[c] = (double)prev;
-    o.asum[c] = (double)asum;
-    o.pmin[c] = n > 0 ? (double)pmin : INFINITY;
-    o.pmax[c] = n > 0 ? (double)pmax : -INFINITY;
-    o.parg[c] = parg;
-    o.sabs[c] = 0.0;
-    o.special[c] = 0;
-    o.ep[c] = o.epoch;
-    if (prev > 0) {
-      o.tbeg[c] = beg; o.tmax[c] = (double)best; o.targ[c] = arg;
-    } else {
-      o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
+    p1_put(o, c, (double)prev, (double)asum, n > 0 ? (double)pmin : INFINITY, n > 0 ? (double)pmax : -INFINITY, parg,
+           0.0, false, beg, (double)best, arg);
+  }
+}
+
+// Chunk c of the FP64 small-k pass from the LDS-staged table s_val; kSumm:
+// with the summaries in the binades of the predicted entry xp.
+template <bool kSumm, bool kTrlr>
+__device__ __forceinline__ void lds_chunk(const Chunks &g, int64_t total, int k, const double *s_val,
+                                          const EmitCfg &ec, uint32_t *__restrict__ visits, const P1 &o,
+                                          const Cand &cand, const SummP1 &sp, int64_t c, double xp) {
+  const uint32_t kmask = (1u << (2 * k)) - 1u;
+  const int64_t start = g.start[c];
+  const int n = g.n[c];
+  const bool first = c == 0 || g.run[c - 1] != g.run[c];
+  P1Lane<kSumm, kTrlr> L;
+  L.init(start, n, first, true, xp);
+  const int64_t q0 = start - k;
+  Window16 win(g.packed, total, q0);
+  for (int b0 = 0; b0 < n; b0 += 16) {
+    const uint64_t x = win.take(q0 + b0);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int i = b0 + j;
+      if (i < n) {
+        const uint32_t code = (uint32_t)(x >> (64 - 2 * (j + k))) & kmask;  // k-mer ending at start + i - 1
+        double s = s_val[code];
+        if (kTrlr && first && i == 0) s = ec.ks[code];  // tr_lr: the run's first k-mer's own score
+        if (visits) atomicAdd(&visits[code], 1u);
+        L.step(s, i, ec, cand);
+      }
     }
   }
+  L.finish(c, o, sp);
 }
 
 // (integer tables on the exact carry take k_pass1_lds_int instead: neither the
@@ -2005,113 +2028,11 @@ __global__ void __launch_bounds__(1024) k_pass1_lds(Chunks g, int64_t total, int
   const int nk = 1 << (2 * k);
   for (int i = threadIdx.x; i < nk; i += blockDim.x) s_val[i] = tv_get(tv, (uint32_t)i);
   __syncthreads();
-  const uint32_t kmask = (uint32_t)nk - 1u;
-  const uint32_t *__restrict__ packed = g.packed;
   for (int64_t c = g.c0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < g.nch;
        c += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t start = g.start[c];
-    const int n = g.n[c];
-    const bool first = c == 0 || g.run[c - 1] != g.run[c];
-    if (xh) {  // pass-1 summaries in the predicted binades (as k_pass1l): the P1Lane form
-      P1Lane<true, kTrlr> L;
-      L.init(start, n, first, true, xh[c]);
-      const int64_t q0 = start - k, last = total >> 4;
-      auto load3 = [&](int64_t q) {
-        const int64_t w = q >> 4;
-        return make_uint3(packed[min(w, last)], packed[min(w + 1, last)], packed[min(w + 2, last)]);
-      };
-      uint3 cur = load3(q0);
-      for (int b0 = 0; b0 < n; b0 += 16) {
-        const uint3 nxt = load3(q0 + b0 + 16);
-        const uint32_t bp = 2u * (uint32_t)((q0 + b0) & 15);
-        const uint64_t x = ((((uint64_t)cur.x << 32) | cur.y) << bp) | (((uint64_t)cur.z << bp) >> 32);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int i = b0 + j;
-          if (i < n) {
-            const uint32_t code = (uint32_t)(x >> (64 - 2 * (j + k))) & kmask;  // k-mer ending at start + i - 1
-            double s = s_val[code];
-            if (kTrlr && first && i == 0) s = ec.ks[code];
-            if (visits) atomicAdd(&visits[code], 1u);
-            L.step(s, i, ec, cand);
-          }
-        }
-        cur = nxt;
-      }
-      L.finish(c, o, sp);
-      continue;
-    }
-    // 16 indices per batch: their k-mers from one 64-bit window of packed
-    // bases (three words, loaded one batch ahead, uniform across the wave)
-    const int64_t q0 = start - k, last = total >> 4;
-    auto load3 = [&](int64_t q) {
-      const int64_t w = q >> 4;
-      return make_uint3(packed[min(w, last)], packed[min(w + 1, last)], packed[min(w + 2, last)]);
-    };
-    uint3 cur = load3(q0);
-    double prev = 0.0, best = 0.0;
-    int beg = -1, arg = 0;
-    double asum = 0.0, pmin = INFINITY, pmax = -INFINITY, sabs = 0.0;
-    int parg = 0;
-    bool special = false;
-    for (int b0 = 0; b0 < n; b0 += 16) {
-      const uint3 nxt = load3(q0 + b0 + 16);
-      const uint32_t bp = 2u * (uint32_t)((q0 + b0) & 15);
-      const uint64_t x = ((((uint64_t)cur.x << 32) | cur.y) << bp) | (((uint64_t)cur.z << bp) >> 32);
-      for (int j = 0; j < 16; ++j) {
-        const int i = b0 + j;
-        if (i >= n) break;
-        const uint32_t code = (uint32_t)(x >> (64 - 2 * (j + k))) & kmask;  // k-mer ending at start + i - 1
-        double s = s_val[code];
-        if (kTrlr && first && i == 0) s = ec.ks[code];  // tr_lr: the run's first k-mer's own score
-        if (visits) atomicAdd(&visits[code], 1u);
-        asum += s;
-        pmin = asum < pmin ? asum : pmin;
-        parg = asum > pmax ? i : parg;
-        pmax = asum > pmax ? asum : pmax;
-        sabs += fabs(s);
-        special |= !isfinite(s);
-        const double tt = prev + s;
-        const double S = tt > 0 ? tt : 0.0;
-        const bool open = (prev == 0) & (S > 0);
-        const bool close = (prev > 0) & (S == 0);
-        const int f0 = first ? 0 : -1;
-        const long long ml = kTrlr ? ec.min_len : 0;
-        const bool want =
-            kTrlr ? (close & (((long long)((arg != f0 ? arg - 1 : arg) - (beg != f0 ? beg - 1 : beg)) >= ml) |
-                              ((long long)((i != f0 ? i - 1 : i) - (arg != f0 ? arg - 1 : arg) - 1) >=
-                               (ml > 1 ? ml : 1LL))))
-                  : (close & ((uint64_t)(int64_t)(arg - beg) >= ec.mw) & (best >= ec.min_score));
-        if (want) {
-          const int64_t slot = append_one(cand.count, cand.segcap);
-          if (slot >= 0) {
-            cand.beg[slot] = start + beg;
-            cand.arg[slot] = start + arg;
-            cand.rst[slot] = start + i;
-            cand.best[slot] = best;
-          }
-        }
-        const bool up = open | (S > best);
-        best = up ? S : best;
-        arg = up ? i : arg;
-        beg = open ? i : (close ? -1 : beg);
-        prev = S;
-      }
-      cur = nxt;
-    }
-    o.cexit[c] = prev;
-    o.asum[c] = asum;
-    o.pmin[c] = pmin;
-    o.pmax[c] = pmax;
-    o.parg[c] = parg;
-    o.sabs[c] = sabs;
-    o.special[c] = special ? 1 : 0;
-    o.ep[c] = o.epoch;
-    if (prev > 0) {
-      o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
-    } else {
-      o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
-    }
+    // xh: pass-1 summaries in the predicted binades (as k_pass1l)
+    if (xh) lds_chunk<true, kTrlr>(g, total, k, s_val, ec, visits, o, cand, sp, c, xh[c]);
+    else lds_chunk<false, kTrlr>(g, total, k, s_val, ec, visits, o, cand, sp, c, 0.0);
   }
 }
 
@@ -3543,6 +3464,22 @@ __global__ void k_fallback_prep(unsigned int *__restrict__ err, unsigned long lo
 
 // ------------------------------------------------------------------- P4
 
+// The carried excursion of a chunk's head: its value T, its maximum hmax with
+// the first argmax harg, and hq, the index of its first clamp (-1: none yet).
+struct Head { double T, hmax; int harg, hq; };
+// Scan index i with value v: nothing moves past the chunk's n indices or
+// after the clamp.  (By value: passed by reference the heads kernels took 12 B
+// of scratch per lane.)
+__device__ __forceinline__ Head head_step(Head h, double v, int i, int n) {
+  if (i < n && h.hq < 0) {
+    const double t = h.T + v;
+    h.T = t > 0 ? t : 0.0;
+    if (h.T == 0.0) h.hq = i;
+    else if (h.T > h.hmax) { h.hmax = h.T; h.harg = i; }
+  }
+  return h;
+}
+
 // Heads of the R chunks (the carried excursion up to its certain clamp):
 // lane per chunk, from the exact entry.  Uncompressed tables read the
 // expanded table (J indices per read) like P1.
@@ -3554,10 +3491,9 @@ __device__ __forceinline__ void head_walk(const Chunks &g, const uint8_t *__rest
   const double x = cr.x[c];
   const int n = g.n[c];
   const int64_t start = g.start[c];
-  double T = x, hmax = -1.0;
-  int harg = 0, hq = -1;
+  Head h{x, -1.0, 0, -1};
   if (kCompressed) {
-    for (int b0 = 0; b0 < n && hq < 0; b0 += NB) {
+    for (int b0 = 0; b0 < n && h.hq < 0; b0 += NB) {
       double v[NB];
       if (!codes) {
         values16_nostore(g, seq, total, k, tv, c, b0, n, v, nullptr);
@@ -3568,15 +3504,7 @@ __device__ __forceinline__ void head_walk(const Chunks &g, const uint8_t *__rest
         for (int j = 0; j < NB; ++j) v[j] = tv.lut[(w[j >> 1] >> (16 * (j & 1))) & 0xffffu];
       }
 #pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        const int i = b0 + j;
-        if (i < n && hq < 0) {
-          const double t = T + v[j];
-          T = t > 0 ? t : 0.0;
-          if (T == 0.0) hq = i;
-          else if (T > hmax) { hmax = T; harg = i; }
-        }
-      }
+      for (int j = 0; j < NB; ++j) h = head_step(h, v[j], b0 + j, n);
     }
   } else if (tv.line) {  // FP64 line table: OWN + 1 indices per read
     const uint32_t mask = (1u << (2 * k)) - 1u;
@@ -3585,20 +3513,12 @@ __device__ __forceinline__ void head_walk(const Chunks &g, const uint8_t *__rest
                                                               : prime_code_guarded(seq, start - k, k, total);
     // (kWide: two batches' reads in flight per round trip; FP64 line tables)
     constexpr int NW = kWide ? 2 * NB : NB;
-    for (int b0 = 0; b0 < n && hq < 0; b0 += NW) {
+    for (int b0 = 0; b0 < n && h.hq < 0; b0 += NW) {
       double v[NW];
       values16_f64(g, seq, total, k, tv, start, b0, n, code, mask, v);
       if (kWide) values16_f64(g, seq, total, k, tv, start, b0 + NB, n, code, mask, v + NB);
 #pragma unroll
-      for (int j = 0; j < NW; ++j) {
-        const int i = b0 + j;
-        if (i < n && hq < 0) {
-          const double t = T + v[j];
-          T = t > 0 ? t : 0.0;
-          if (T == 0.0) hq = i;
-          else if (T > hmax) { hmax = T; harg = i; }
-        }
-      }
+      for (int j = 0; j < NW; ++j) h = head_step(h, v[j], b0 + j, n);
     }
   } else {
     constexpr int G = (J == 1) ? 16 : (J == 4 ? 4 : 8);
@@ -3609,7 +3529,7 @@ __device__ __forceinline__ void head_walk(const Chunks &g, const uint8_t *__rest
     uint64_t xp = 0;
     uint32_t gcode = packed_bits(packed, total, start - k, xp) ? (uint32_t)(xp >> (64 - 2 * kx))
                                                                : prime_code_guarded(seq, start - k, kx, total);
-    for (int b0 = 0; b0 < n && hq < 0; b0 += PB) {
+    for (int b0 = 0; b0 < n && h.hq < 0; b0 += PB) {
       uint32_t gc[G];
       uint64_t xb = 0;
       if (2 * PB <= 64 && packed_bits(packed, total, start + b0 + J - 1, xb)) {
@@ -3652,21 +3572,13 @@ __device__ __forceinline__ void head_walk(const Chunks &g, const uint8_t *__rest
         }
       }
 #pragma unroll
-      for (int j = 0; j < PB; ++j) {
-        const int i = b0 + j;
-        if (i < n && hq < 0) {
-          const double t = T + v[j];
-          T = t > 0 ? t : 0.0;
-          if (T == 0.0) hq = i;
-          else if (T > hmax) { hmax = T; harg = i; }
-        }
-      }
+      for (int j = 0; j < PB; ++j) h = head_step(h, v[j], b0 + j, n);
     }
   }
-  if (hq < 0) atomicOr(err, 2u);  // predicted clamp did not happen
-  cr.hq[c] = hq;
-  cr.hmax[c] = hmax;
-  cr.harg[c] = harg;
+  if (h.hq < 0) atomicOr(err, 2u);  // predicted clamp did not happen
+  cr.hq[c] = h.hq;
+  cr.hmax[c] = h.hmax;
+  cr.harg[c] = h.harg;
 }
 
 template <int J, bool kCompressed, bool kWide = false>

@@ -729,3 +729,83 @@ def test_many_regions_pinned_output_block(oracle, ctx):
             del pos, sc  # (the block goes back to the library's keep list)
     finally:
         tab.close()
+
+
+# ------------------------------------------- pass-1 kernels at the chunk seams
+
+_CH = 256  # scan indices per chunk of the chunked scan
+
+_P1_FORMS = [
+    # small k, no expanded table and so no binade predictor: k_pass1_lds without summaries
+    ("lds-nopredictor", 6, True, False, {}),
+    # unexpanded tables at larger k: k_pass1<1, ...>, with and without the code store
+    ("plain-u16", 9, True, False, {}),
+    ("plain-f64", 9, False, False, {}),
+    # expanded compressed table: k_pass1p, and k_pass1<J, ...> on the chunks near the buffer end
+    ("expanded-tail", 9, True, True, {"KS_NO_LINES": "1"}),
+]
+
+
+def _seam_genome(k, rng):
+    """< 100 kbp in two sequences: a run shorter than one chunk that ends in
+    poly-A (every excursion in it closes), runs of about one chunk (CH - 2 ..
+    CH + 2 scan indices whichever way a mode counts them), runs shorter than
+    k, N gaps, long runs, and a last run that ends with the buffer."""
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    run = lambda n: acgt[rng.integers(0, 4, size=n)].tobytes()  # noqa: E731
+    short = run(150) + b"A" * (2 * k)
+    parts = [short, b"NNNNN"]
+    for d in range(-2, 3):
+        parts += [run(_CH + k + d), b"N"]
+    parts += [b"N" * 40, run(k - 1), b"N", run(3), b"NN", run(60_000), b"N" * 300, run(30_000)]
+    return short, [b"".join(parts), run(2_000)]
+
+
+@pytest.mark.parametrize("mode", ["kmer_regions", "tr_lr"])
+@pytest.mark.parametrize("form,k,compress,expand,env", _P1_FORMS, ids=[f[0] for f in _P1_FORMS])
+def test_pass1_chunk_seams(oracle, ctx, monkeypatch, form, k, compress, expand, env, mode):
+    """Every pass-1 kernel shares one per-index walk: the forms no other test
+    runs with the chunked scan forced (above), both emission rules, on runs at
+    the chunk seams.  Regions and score bits equal the oracle's, and so do the
+    visits for kmer_regions (tr_lr takes no visit histogram).  The scan's
+    statistics hold no candidate count, so that the candidate list is not
+    empty is asserted by proxy: the oracle finds regions in the single-chunk
+    run alone, whose poly-A end closes every excursion inside chunk 0, and a
+    region closed inside one chunk can only come from a pass-1 candidate."""
+    import torch
+    from kmer_spans_amd import device as D
+    for name, value in env.items():  # before the tables: KS_NO_LINES is read at table build
+        monkeypatch.setenv(name, value)
+    rng = np.random.default_rng(100 + k)
+    short, host = _seam_genome(k, rng)
+    assert sum(len(s) for s in host) <= 100_000 and oracle.kmer_seq(k)[0] == "A" * k
+    ds = D.from_host(host, "cuda")
+    D.bind_torch_stream(ctx)
+    w = rng.normal(-0.2, 1.0, 4 ** k)
+    w[0] = -50.0  # poly-A closes every excursion
+    tab = D.DeviceTable(ctx, w, k, 0.0, compress=compress, expand=expand)
+    assert (tab.positions_per_read > 1) == expand
+    tks = None
+    ctx.set_scan_algo(1)
+    try:
+        if mode == "kmer_regions":
+            o = oracle.scan(host, k, w, 0.0, 3, 1.0, visits=True)
+            cand = oracle.scan([short], k, w, 0.0, 3, 1.0)["pos"]
+            vis = torch.zeros(4 ** k, dtype=torch.int32, device="cuda")
+            pos, sc, st = D.scan(ctx, ds, k, tab, 3, 1.0, vis)
+            assert np.array_equal(vis.cpu().numpy(), o["counts"]), (form, mode)
+        else:
+            ks = rng.normal(size=4 ** k)
+            tks = D.DeviceTable(ctx, ks, k, 0.0, compress=False)
+            o = oracle.tr_lr_regions(host, k, 3, ks, w)
+            cand = oracle.tr_lr_regions([short], k, 3, ks, w)["pos"]
+            pos, sc, st = D.tr_lr(ctx, ds, k, tab, tks, 3)
+        assert st["scan_algo"] == 1
+        assert cand.shape[1] > 0, "no closed candidate in the single-chunk run"
+        _assert_same_regions(pos, sc, o["pos"], o["score"], (form, mode))
+        assert o["pos"].shape[1] > 100
+    finally:
+        ctx.set_scan_algo(-1)
+        tab.close()
+        if tks is not None:
+            tks.close()
