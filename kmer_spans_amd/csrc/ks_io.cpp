@@ -163,14 +163,17 @@ ks_status fasta_from_view(ks_ctx *ctx, const HostView &v, const char *what, int6
   const double t1 = now_ms();
   FastaParse fp;
   KS_TRY(fasta_parse_dev(ctx, d_raw, (int64_t)v.n, &fp));
+  // A sequential reader stops at the first kept byte when no record has
+  // started, whatever that byte is; err_pos is a kept byte too (first_kept <=
+  // err_pos), so this comes first.
+  if (fp.first_kept >= 0 && (fp.first_hdr < 0 || fp.first_kept < fp.first_hdr))
+    return fail(KS_ERR_ARG, "reading FASTA %s: sequence data before the first description line (line %lld)", what,
+                (long long)line_of(v, fp.first_kept));
   if (fp.err_pos >= 0) {
     const uint8_t c = v.p[fp.err_pos];
     return fail(KS_ERR_ARG, "reading FASTA %s: invalid one-letter sequence code '%c' (0x%02x) at line %lld", what,
                 (c >= 32 && c < 127) ? c : '?', c, (long long)line_of(v, fp.err_pos));
   }
-  if (fp.first_kept >= 0 && (fp.first_hdr < 0 || fp.first_kept < fp.first_hdr))
-    return fail(KS_ERR_ARG, "reading FASTA %s: sequence data before the first description line (line %lld)", what,
-                (long long)line_of(v, fp.first_kept));
   struct Guard {
     FastaParse *fp;
     ~Guard() {
