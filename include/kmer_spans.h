@@ -344,6 +344,11 @@ typedef struct ks_scan_stats {
   double ms_carry;      /* P3/P4: exact carry, heads */
   double ms_stitch;     /* P5: excursion stitch, candidates */
 } ks_scan_stats;
+/* The chunked scan's units (tests place seams with them): scan indices per
+ * chunk, one lane each, and chunks per tile of the carry, the prescan and the
+ * stitch.  One trip of the per-run wave loops takes 64 tiles. */
+int32_t ks_scan_chunk_indices(void);
+int32_t ks_scan_tile_chunks(void);
 
 /* Span scan of device-resident sequences (the hot path).  visits_dev: device
  * int32[4^k] accumulated (caller zeroes), or NULL.  Regions are returned in

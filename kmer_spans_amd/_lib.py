@@ -137,6 +137,7 @@ EXPORTS = [
     "ks_nj", "ks_nj_dev", "ks_nj_edges",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
+    "ks_scan_chunk_indices", "ks_scan_tile_chunks",
 ]
 
 KS_SPECTRA_MAX_Q = 6
@@ -233,6 +234,8 @@ def load():
         "ks_seq_index_info_get": ([P, P], I32),
         "ks_scan_dev_indexed": ([P, P, P, I32, P, I32, D, P, P, P], I32),
         "ks_tr_lr_dev_indexed": ([P, P, P, I32, P, P, I32, P, P], I32),
+        "ks_scan_chunk_indices": ([], I32),
+        "ks_scan_tile_chunks": ([], I32),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

@@ -4965,6 +4965,11 @@ ks_status debug_rescan_hist(const Rescan &rs, const unsigned long long *counts, 
   return KS_OK;
 }
 
+static_assert(CH == kChunk, "the scan's chunk is the layout's chunk (ks_runs.hip cuts the runs by kChunk)");
+
 }  // namespace
 
 }  // namespace ks
+
+extern "C" int32_t ks_scan_chunk_indices(void) { return ks::CH; }
+extern "C" int32_t ks_scan_tile_chunks(void) { return ks::kTileChunks; }
