@@ -323,6 +323,33 @@ typedef struct ks_table_info {
 } ks_table_info;
 ks_status ks_table_get_info(const ks_table *t, ks_table_info *out);
 
+/* A read-only window into a built table (tests compare every built form
+ * with a host model of its layout).  None of these launches a kernel or
+ * writes to the device.  Parts: */
+#define KS_TABLE_PART_VALS 0    /* FP64 s, 4^k (uncompressed tables)                  */
+#define KS_TABLE_PART_CODES 1   /* uint16 codes, 4^k (compressed tables)              */
+#define KS_TABLE_PART_LUT 2     /* FP64 value of every code, distinct entries         */
+#define KS_TABLE_PART_EXT 3     /* the expanded table or the line table               */
+#define KS_TABLE_PART_RLINES 4  /* weighted-rank 128-B code lines                     */
+#define KS_TABLE_PART_RPIECES 5 /* rank pieces: pairs of uint64 (base bits, increment) */
+#define KS_TABLE_PART_LUT12 6   /* FP64[4096]: the values of the 12-bit codes         */
+#define KS_TABLE_PART_MAP12 7   /* uint16[4096]: 12-bit code -> uint16 code           */
+#define KS_TABLE_PART_APPROX 8  /* FP16 bits per approx_k-base prefix                 */
+/* Bytes of a part; 0 when the table does not have it (or part is unknown). */
+int64_t ks_table_debug_bytes(const ks_table *t, int32_t part);
+/* Synchronous copy of bytes [offset, offset + nbytes) of a part to host
+ * memory, on the table's device; a range outside the part is KS_ERR_ARG. */
+ks_status ks_table_debug_read(const ks_table *t, int32_t part, int64_t offset, int64_t nbytes, void *dst_host);
+typedef struct ks_table_props {
+  int32_t int_exact;      /* every s is a finite integer of magnitude <= 2^20   */
+  int32_t no_nan_posinf;  /* no s is NaN or +Inf                                */
+  double max_abs;         /* max |s| over the finite values                     */
+  int32_t ext_J, ext_bits;        /* as built (1, 16 without an expanded form) */
+  int32_t line_kind, line_own;    /* of the table in KS_TABLE_PART_EXT         */
+  int32_t approx_k, n_rpieces;
+} ks_table_props;
+ks_status ks_table_debug_props(const ks_table *t, ks_table_props *out);
+
 /* Scan statistics of the last ks_scan_dev call (device time of each phase,
  * measured with hipEvents on the ctx stream). */
 typedef struct ks_scan_stats {

@@ -66,6 +66,21 @@ class TableInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class TableProps(C.Structure):
+    _fields_ = [("int_exact", C.c_int32), ("no_nan_posinf", C.c_int32), ("max_abs", C.c_double),
+                ("ext_J", C.c_int32), ("ext_bits", C.c_int32), ("line_kind", C.c_int32), ("line_own", C.c_int32),
+                ("approx_k", C.c_int32), ("n_rpieces", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+# KS_TABLE_PART_* of ks_table_debug_bytes / ks_table_debug_read, with the element type of each part
+TABLE_PARTS = {"vals": (0, np.float64), "codes": (1, np.uint16), "lut": (2, np.float64), "ext": (3, np.uint8),
+               "rlines": (4, np.uint32), "rpieces": (5, np.uint64), "lut12": (6, np.float64),
+               "map12": (7, np.uint16), "approx": (8, np.uint16)}
+
+
 class SpectraStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_plan", C.c_double), ("ms_count", C.c_double),
                 ("ms_entropy", C.c_double), ("n_regions", C.c_int64), ("n_bases", C.c_int64),
@@ -122,7 +137,7 @@ EXPORTS = [
     "ks_low_comp_regions", "ks_kmer_seq", "ks_rank_table", "ks_log2_table", "ks_pm1_table",
     "ks_table_create", "ks_table_destroy", "ks_table_is_compressed", "ks_table_distinct",
     "ks_table_positions_per_read", "ks_table_create_hint", "ks_table_code_bits", "ks_table_escape_fraction",
-    "ks_table_get_info",
+    "ks_table_get_info", "ks_table_debug_bytes", "ks_table_debug_read", "ks_table_debug_props",
     "ks_scan_dev", "ks_count_dev", "ks_ctx_set_scan_algo", "ks_tr_lr_regions", "ks_tr_lr_dev",
     "ks_fasta_load", "ks_fasta_parse", "ks_fasta_copy_seqs", "ks_fasta_free", "ks_count_multi_dev",
     "ks_count_file_write", "ks_count_file_read", "ks_count_file_free", "ks_kmers_to_file",
@@ -188,6 +203,9 @@ def load():
         "ks_table_code_bits": ([P], I32),
         "ks_table_escape_fraction": ([P], D),
         "ks_table_get_info": ([P, P], I32),
+        "ks_table_debug_bytes": ([P, I32], I64),
+        "ks_table_debug_read": ([P, I32, I64, I64, P], I32),
+        "ks_table_debug_props": ([P, P], I32),
         "ks_scan_dev": ([P, P, I32, P, I32, D, P, P, P], I32),
         "ks_count_dev": ([P, P, I32, P, P], I32),
         "ks_tr_lr_regions": ([P, P, P, I32, I32, I32, P, P, P, I64, P, P], I32),

@@ -1665,6 +1665,67 @@ extern "C" ks_status ks_table_get_info(const ks_table *t, ks_table_info *out) {
   return KS_OK;
 }
 
+// The test window (include/kmer_spans.h): where a part lies and how long it is.
+static const void *table_part(const ks_table *t, int32_t part, int64_t *bytes) {
+  const int64_t n = (int64_t)1 << (2 * t->k);
+  const void *p = nullptr;
+  int64_t b = 0;
+  switch (part) {
+    case KS_TABLE_PART_VALS: p = t->d_vals; b = n * 8; break;
+    case KS_TABLE_PART_CODES: p = t->d_codes; b = n * 2; break;
+    case KS_TABLE_PART_LUT: p = t->d_lut; b = t->distinct * 8; break;
+    case KS_TABLE_PART_EXT: p = t->d_ext; b = (int64_t)t->ext_bytes; break;
+    case KS_TABLE_PART_RLINES: p = t->d_rlines; b = (int64_t)t->rlines_bytes; break;
+    case KS_TABLE_PART_RPIECES: p = t->d_rpieces; b = (int64_t)t->n_rpieces * 16; break;
+    case KS_TABLE_PART_LUT12: p = t->d_lut12; b = 4096 * 8; break;
+    case KS_TABLE_PART_MAP12: p = t->d_map12; b = 4096 * 2; break;
+    case KS_TABLE_PART_APPROX: p = t->d_approx; b = (int64_t)2 << (2 * t->approx_k); break;
+    default: break;
+  }
+  *bytes = p && b > 0 ? b : 0;
+  return *bytes ? p : nullptr;
+}
+
+extern "C" int64_t ks_table_debug_bytes(const ks_table *t, int32_t part) {
+  int64_t b = 0;
+  if (t) (void)table_part(t, part, &b);
+  return b;
+}
+
+extern "C" ks_status ks_table_debug_read(const ks_table *t, int32_t part, int64_t offset, int64_t nbytes,
+                                         void *dst_host) {
+  if (!t || !dst_host) return fail(KS_ERR_ARG, "ks_table_debug_read: null argument");
+  int64_t b = 0;
+  const void *p = table_part(t, part, &b);
+  if (!p) return fail(KS_ERR_ARG, "ks_table_debug_read: the table has no part %d", part);
+  if (offset < 0 || nbytes < 0 || offset > b || nbytes > b - offset)
+    return fail(KS_ERR_ARG, "ks_table_debug_read: bytes [%lld, %lld + %lld) outside the part's %lld",
+                (long long)offset, (long long)offset, (long long)nbytes, (long long)b);
+  if (nbytes == 0) return KS_OK;
+  int cur = -1;
+  KS_HIP(hipGetDevice(&cur));
+  KS_HIP(hipSetDevice(t->device));
+  const hipError_t e = hipMemcpy(dst_host, static_cast<const char *>(p) + offset, (size_t)nbytes, hipMemcpyDeviceToHost);
+  if (cur >= 0) (void)hipSetDevice(cur);
+  KS_HIP(e);
+  return KS_OK;
+}
+
+extern "C" ks_status ks_table_debug_props(const ks_table *t, ks_table_props *out) {
+  if (!t || !out) return fail(KS_ERR_ARG, "null argument");
+  memset(out, 0, sizeof(*out));
+  out->int_exact = t->int_exact ? 1 : 0;
+  out->no_nan_posinf = t->no_nan_posinf ? 1 : 0;
+  out->max_abs = t->max_abs;
+  out->ext_J = t->ext_J;
+  out->ext_bits = t->ext_bits;
+  out->line_kind = t->line_kind;
+  out->line_own = t->line_own;
+  out->approx_k = t->approx_k;
+  out->n_rpieces = t->n_rpieces;
+  return KS_OK;
+}
+
 extern "C" double ks_table_escape_fraction(const ks_table *t) {
   // 12-bit (k+4)-mer tables: share of scan indices that escape; wide lines
   // (13): share of the L3 indices (one per line) that escape

@@ -223,6 +223,27 @@ class DeviceTable:
     def distinct(self) -> int:
         return int(load().ks_table_distinct(self._h))
 
+    def debug_bytes(self, part: str) -> int:
+        """ks_table_debug_bytes: bytes of a part (_lib.TABLE_PARTS), 0 when the table has none."""
+        return int(load().ks_table_debug_bytes(self._h, _lib.TABLE_PARTS[part][0]))
+
+    def debug_read(self, part: str, lo: int = 0, n: int | None = None, dtype=None) -> np.ndarray:
+        """ks_table_debug_read: elements [lo, lo + n) of a part (to its end by
+        default) as a numpy array of the part's element type, or of dtype."""
+        pid, dt = _lib.TABLE_PARTS[part]
+        dt = np.dtype(dtype or dt)
+        if n is None:
+            n = self.debug_bytes(part) // dt.itemsize - lo
+        out = np.empty(max(int(n), 1), dtype=dt)  # (a bad range is the library's error, an empty one too)
+        check(load().ks_table_debug_read(self._h, pid, int(lo) * dt.itemsize, int(n) * dt.itemsize, out.ctypes.data))
+        return out[:max(int(n), 0)]
+
+    def debug_props(self) -> dict:
+        """ks_table_debug_props: the flags and the raw form of the built table."""
+        p = _lib.TableProps()
+        check(load().ks_table_debug_props(self._h, C.byref(p)))
+        return p.as_dict()
+
     def close(self):
         if self._h:
             load().ks_table_destroy(self._h)
