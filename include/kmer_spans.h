@@ -419,7 +419,21 @@ ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, const ks
  * The _indexed entries return KS_ERR_ARG when seqs does not match the handle
  * (pointers, nseq, offsets).  ix == NULL, or KS_NO_SEQ_INDEX set in the
  * environment (read per call), makes them the plain entries.  ks_scan_dev
- * and ks_tr_lr_dev always recompute.  On a hit ks_scan_stats.ms_runs is 0. */
+ * and ks_tr_lr_dev always recompute.  On a hit ks_scan_stats.ms_runs is 0.
+ *
+ * The chunked scan keeps two more things of a handle's last scan on the
+ * context, in a workspace slot of their own.  The chunk table (start, length
+ * and run of every 256-index chunk, the run of every tile) depends on the
+ * runs, k and the scan kind only: a hit with the same k and scan kind takes it
+ * as it is (chunk_reuses).  The entry hint is the value each chunk was
+ * predicted to be entered with, from which pass 1 picks the binade it
+ * summarises in; a scan with the same table(s) as the previous one takes the
+ * prediction that scan made from its exact pass-1 results instead of running
+ * the predictor (hint_reuses).  Tables are told apart by a process-unique id,
+ * never by address.  A hint is only a hint: a wrong one costs gathered
+ * summaries or replays (ks_scan_stats.n_replay may differ from a scan without
+ * it), never a region, a score or a visit count.  KS_NO_CHUNK_REUSE=1 and
+ * KS_NO_ENTRY_HINT=1 (read per call) switch either off. */
 typedef struct ks_seq_index ks_seq_index;
 ks_status ks_seq_index_create(const ks_dev_seqs *seqs, ks_seq_index **out);
 void ks_seq_index_destroy(ks_seq_index *ix);
@@ -429,6 +443,10 @@ typedef struct ks_seq_index_info {
   int64_t layout_builds;  /* indexed calls that computed the chunk layout (every
                              build, and a hit with another k or scan kind)          */
   int64_t guard_failures; /* hit calls failed by the check against the bytes        */
+  /* chunked scans with the handle that succeeded (see below) */
+  int64_t chunk_reuses;     /* took the chunk table of the context's previous scan  */
+  int64_t hint_reuses;      /* took its entry hint too: no predictor                */
+  int64_t predictor_builds; /* ran the predictor (pass-1-summary tables only)       */
 } ks_seq_index_info;
 ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_info *out);
 ks_status ks_scan_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *seqs, ks_seq_index *ix, int32_t k,

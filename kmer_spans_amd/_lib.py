@@ -49,10 +49,13 @@ class ScanStats(C.Structure):
 
 class SeqIndexInfo(C.Structure):
     _fields_ = [("builds", C.c_int64), ("hits", C.c_int64), ("layout_builds", C.c_int64),
-                ("guard_failures", C.c_int64)]
+                ("guard_failures", C.c_int64), ("chunk_reuses", C.c_int64), ("hint_reuses", C.c_int64),
+                ("predictor_builds", C.c_int64)]
+    INDEX_FIELDS = ("builds", "hits", "layout_builds", "guard_failures")
+    SCAN_FIELDS = ("chunk_reuses", "hint_reuses", "predictor_builds")
 
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+    def as_dict(self, fields=None):
+        return {f: int(getattr(self, f)) for f in (fields or [f for f, _ in self._fields_])}
 
 
 class TableInfo(C.Structure):

@@ -157,6 +157,11 @@ ks_status ctx_busy() {
 // (debug_poison_workspace), and the table-side allocations (ks_table.hip:
 // table values / codes / LUT, predictor table, expanded and line tables
 // including pooled buffers taken again).
+uint64_t next_table_id() {
+  static std::atomic<uint64_t> g_table_id{0};
+  return ++g_table_id;
+}
+
 int debug_poison_byte() {
   static const int poison = getenv("KS_DEBUG_POISON") ? (int)strtol(getenv("KS_DEBUG_POISON"), nullptr, 0) : -1;
   return poison;
@@ -214,6 +219,7 @@ ks_status ensure(ks_ctx *ctx, Slot s, size_t bytes, void **out) {
   if (b.bytes < bytes) {
     // a sequence index's data does not survive a new buffer for one of its slots
     if (s == SLOT_PACKED || s == SLOT_RUNS || s == SLOT_LAYOUT) seq_cache_clear(ctx);
+    if (s == SLOT_CHUNK_KEEP) chunk_keep_clear(ctx);  // (the kept chunk table and hint go with their buffer)
     if (b.ptr) {
       // every stream of the context may still use the old buffer (the
       // piecewise count of a host entry runs on the side stream, pass 1's
@@ -707,6 +713,7 @@ extern "C" ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *s, int32_t k, 
   ScanMode mode;
   mode.trlr = 1;
   mode.ks = init->d_vals;
+  mode.init_id = init->id;
   mode.min_len = min_length;
   mode.finite = trans->no_nan_posinf && init->no_nan_posinf;
   mode.maxabs = std::max(trans->max_abs, init->max_abs);
@@ -738,6 +745,9 @@ extern "C" ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_
   out->hits = ix->hits;
   out->layout_builds = ix->layout_builds;
   out->guard_failures = ix->guard_failures;
+  out->chunk_reuses = ix->chunk_reuses;
+  out->hint_reuses = ix->hint_reuses;
+  out->predictor_builds = ix->predictor_builds;
   return KS_OK;
 }
 
@@ -785,6 +795,7 @@ extern "C" ks_status ks_tr_lr_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *s, ks_
   KS_ENTER(ctx);
   mode.trlr = 1;
   mode.ks = init->d_vals;
+  mode.init_id = init->id;
   mode.min_len = min_length;
   mode.finite = trans->no_nan_posinf && init->no_nan_posinf;
   mode.maxabs = std::max(trans->max_abs, init->max_abs);
@@ -856,6 +867,7 @@ extern "C" ks_status ks_tr_lr_regions(ks_ctx *ctx, const char *const *seqs, cons
     ScanMode mode;
     mode.trlr = 1;
     mode.ks = t_ks->d_vals;
+    mode.init_id = t_ks->id;
     mode.min_len = min_length;
     mode.finite = t_tr->no_nan_posinf && t_ks->no_nan_posinf;
     mode.maxabs = std::max(t_tr->max_abs, t_ks->max_abs);

@@ -67,6 +67,7 @@ enum Slot : int {
   SLOT_PACKED,      // 2-bit base codes of the whole buffer (find_runs, want_packed)
   SLOT_STAGE_NIB,   // host entry staging: 4-bit base classes as sent over PCIe
   SLOT_RANKS,       // host low-comp entry: the weighted-rank vector (FP64 [4^k]) on its way out
+  SLOT_CHUNK_KEEP,  // chunked scan: chunk table, tile map and entry hints, kept between scans (ChunkKeep)
   SLOT_COUNT
 };
 
@@ -132,6 +133,30 @@ struct SeqCache {
   int k = 0, trlr = 0;  // what lay was built for
 };
 
+// What a context's SLOT_CHUNK_KEEP holds of the last chunked scan of a
+// sequence index (only scan_chunked writes that slot): the chunk table
+// (Chunks::start / n / run) and the tile map (Work::trun), which depend on
+// the cached runs and layout, k and trlr only, and the entry hint, P2's
+// predicted entries of that call (Work::xt), which depend on the table(s)
+// too.  id 0: nothing.  chunk_keep_clear is the only way the tag goes away:
+// with the sequence cache's tag (seq_cache_clear), where ensure regrows the
+// slot, and at the top of every scan_chunked call, which sets it again only
+// when it returns KS_OK.
+struct ChunkKeep {
+  uint64_t id = 0;  // ks_seq_index::id
+  int k = 0, trlr = 0;
+  int64_t nch = 0, ntiles = 0;
+  const void *base = nullptr;  // the slot's buffer when the tag was set
+  // the hint: the table it was computed with (tr_lr: the transition table
+  // and the first-k-mer table) and which of the two hint arrays holds it
+  uint64_t table_id = 0, init_id = 0;
+  int hint = -1;  // -1: none
+};
+
+// Process-unique id of a score table (ks_table::id, never 0): a table
+// destroyed and created again at the same address is another table.
+uint64_t next_table_id();
+
 }  // namespace ks
 
 struct ks_ctx {
@@ -168,6 +193,7 @@ struct ks_ctx {
   bool chunked_events = false;  // the last scan_chunked recorded its phase events (ev[7..11], ev[14..15])
   bool vis_count_ext_used = false;
   ks::SeqCache seq_cache;  // (ks_runs.hip: find_runs / run_layout; cleared wherever the three slots go)
+  ks::ChunkKeep chunk_keep;  // (ks_scan_chunked.hip; cleared with seq_cache and wherever its slot goes)
 };
 
 // A sequence index (include/kmer_spans.h): a host record of which sequences
@@ -180,9 +206,13 @@ struct ks_seq_index {
   int32_t nseq = 0;
   std::vector<int64_t> offsets;  // copy of offsets_host
   int64_t builds = 0, hits = 0, layout_builds = 0, guard_failures = 0;
+  // chunked scans with this index that returned KS_OK: chunk table taken from the kept slot,
+  // entry hint taken from it, predictor run (pass-1-summary path without a hint)
+  int64_t chunk_reuses = 0, hint_reuses = 0, predictor_builds = 0;
 };
 
 struct ks_table {
+  uint64_t id = ks::next_table_id();
   ks_ctx *ctx = nullptr;
   int k = 0;
   double thr = 0;
@@ -408,7 +438,13 @@ ks_status run_layout(ks_ctx *ctx, const Runs &runs, int k, RunLayout *lay, int t
 // The context's SLOT_PACKED / SLOT_RUNS / SLOT_LAYOUT no longer hold what
 // ctx->seq_cache says: called at the top of find_runs and run_layout and
 // wherever those slots are freed, regrown or poisoned.
-inline void seq_cache_clear(ks_ctx *ctx) { ctx->seq_cache = SeqCache(); }
+// The context's SLOT_CHUNK_KEEP no longer holds what ctx->chunk_keep says.
+inline void chunk_keep_clear(ks_ctx *ctx) { ctx->chunk_keep = ChunkKeep(); }
+// (the chunk table is built from the cached runs and layout: its tag goes with theirs)
+inline void seq_cache_clear(ks_ctx *ctx) {
+  ctx->seq_cache = SeqCache();
+  chunk_keep_clear(ctx);
+}
 // Hit path of a sequence index: checks the cached runs (ends against the
 // bytes and the offsets) and one packed word per 64 KiB against the bytes, on
 // ctx->stream; a mismatch stores 1 to *flag_dev (zeroed by the caller in
@@ -470,6 +506,9 @@ struct ScanMode {
   bool visits_counted = false;
   // sequence index of an _indexed entry (nullptr: a plain call, always recomputes)
   ks_seq_index *index = nullptr;
+  // ks_table::id of the scanned table (set by scan_core) and of the tr_lr
+  // first-k-mer table behind ks (0: none): the key of the kept entry hint
+  uint64_t table_id = 0, init_id = 0;
 };
 
 ks_status scan_impl(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int k, const ks_table *t,

@@ -465,8 +465,10 @@ static ks_status scan_core(ks_ctx *ctx, const ks_dev_seqs *s, int64_t total, int
       // unless KS_VISITS_ATOMIC is set (one random atomic per scanned index in
       // pass 1, the former path, kept for A/B runs and tests)
       const bool vis_atomic = getenv("KS_VISITS_ATOMIC") != nullptr;
+      ScanMode cmode = mode;
+      cmode.table_id = t->id;  // (the key of the kept entry hint, with mode.init_id)
       ks_status rc = scan_chunked(ctx, s, runs, lay, k, tv, mw, min_score, vis_atomic ? vscr : nullptr, vscr, rb, S,
-                                  mode);
+                                  cmode);
       // (stale runs can make any of the scan's own checks fail: the guard's verdict first)
       if (hit && ctx->hreg_ok && ctx->hguard != 0) return guard_failed();
       if (rc == KS_INTERNAL_RETRY) {  // a buffer did not fit: grow, rerun, visits untouched

@@ -32,6 +32,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -3936,12 +3937,27 @@ __global__ void k_candidates(Chunks g, const int64_t *__restrict__ ra, const int
   emit_wave(e, out, rs, sid, best);
 }
 
+// KS_TEST_ENTRY_HINT (tests): the entry hint of a call that reuses one,
+// overwritten before its pass 1.  what 0: zero, 1: 1e14, 2: NaN, 3: chunk c
+// gets chunk c + 1's value from src, a copy of the hint taken beforehand.
+__global__ void __launch_bounds__(256) k_test_hint(double *__restrict__ xh, const double *__restrict__ src,
+                                                   int64_t nch, int what) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nch) return;
+  double v = 0.0;
+  if (what == 1) v = 1.0e14;
+  if (what == 2) v = __longlong_as_double(0x7ff8000000000000LL);
+  if (what == 3) v = src[c + 1 < nch ? c + 1 : c];
+  xh[c] = v;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------ host driver
 //
 // scan_chunked reads top to bottom: plan (plan_scan: which path the call
-// takes) -> workspace (carve) -> layout kernels -> predictor -> pass 1 ->
+// takes) -> kept slot (carve_keep: what the previous scan left) -> workspace
+// (carve) -> layout kernels -> predictor (either only without it) -> pass 1 ->
 // post-processing and rescans per half -> counter read-back -> retry
 // decisions.  The helpers before it launch; none of them decides a path.
 namespace {
@@ -4133,12 +4149,41 @@ struct Carver {
   }
 };
 
-// The call's buffers: SLOT_CHUNK_A carved (carve), the code store, the
-// candidate and rescan lists of each half, the diagnostics' counters.
+// SLOT_CHUNK_KEEP carved (carve_keep): what a later scan of the same
+// sequence index may take as it is (ChunkKeep, ks_internal.h).  No kernel
+// writes start / n / run / trun after P0 (k_make_chunks, k_tile_runs), and
+// none writes a hint array after the scan that filled it (P0's or P2's ascan).
+struct Keep {
+  int64_t *start;
+  int32_t *n, *run;
+  int32_t *trun;  // stitch tile -> run (k_tile_runs)
+  // the two hint arrays: one is the call's Work::xh (read by pass 1), the
+  // other its Work::xt (written by P2); a call that takes xh from the previous
+  // call's xt writes the other array, so the roles swap from call to call and
+  // P2 of the first part never overwrites what the second part's pass 1 reads
+  double *hint[2];
+};
+
+Keep carve_keep(char *base, int64_t nch, int64_t ntiles, size_t *bytes) {
+  Carver cv{base};
+  Keep kp{};
+  kp.start = cv.take<int64_t>(nch);
+  kp.n = cv.take<int32_t>(nch);
+  kp.run = cv.take<int32_t>(nch);
+  kp.trun = cv.take<int32_t>(ntiles + 1);
+  kp.hint[0] = cv.take<double>(nch);
+  kp.hint[1] = cv.take<double>(nch);
+  *bytes = cv.off;
+  return kp;
+}
+
+// The call's buffers: SLOT_CHUNK_A carved (carve), the kept slot's arrays,
+// the code store, the candidate and rescan lists of each half, the
+// diagnostics' counters.
 struct Work {
   Chunks g;
   P1 p1;
-  double *xt;  // predicted entries (P2 prescan)
+  double *xt;  // predicted entries (P2 prescan): one of Keep::hint
   Summ sm;
   Carry cr;
   // cnts: [0, kSegs) candidate counters, [kSegs, 2 kSegs) rescan counters,
@@ -4153,7 +4198,7 @@ struct Work {
   // the summaries, the fix list (nfix[2]: one counter per half)
   double *pa, *pb;
   uint8_t *pz;
-  double *xh;
+  double *xh;  // the other of Keep::hint: P0's prediction, or the previous call's xt
   SummP1 sp1;
   unsigned long long *nfix;
   int64_t *fix;
@@ -4172,17 +4217,15 @@ struct Work {
   int64_t nwin = 0;
 };
 
-// SLOT_CHUNK_A's layout.  base null: the size alone.
-Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const uint32_t *packed, size_t *bytes) {
+// SLOT_CHUNK_A's layout.  base null: the size alone.  xt and xh are the
+// caller's choice among kp.hint.
+Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const uint32_t *packed, const Keep &kp,
+           size_t *bytes) {
   Carver cv{base};
-  int64_t *start = cv.take<int64_t>(nch);
-  int32_t *n = cv.take<int32_t>(nch);
-  int32_t *run = cv.take<int32_t>(nch);
   double *p1d = cv.take<double>(nch * 6);
   int32_t *p1i = cv.take<int32_t>(nch * 3);
   uint8_t *spec = cv.take<uint8_t>(nch);
   uint32_t *ep = cv.take<uint32_t>(nch);
-  double *xt = cv.take<double>(nch);
   int32_t *se = cv.take<int32_t>(nch);
   long long *sD = cv.take<long long>(nch * 6);
   int32_t *sA = cv.take<int32_t>(nch * 2);
@@ -4196,7 +4239,6 @@ Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const 
   double *pa = cv.take<double>(nch);
   double *pb = cv.take<double>(nch);
   uint8_t *pz = cv.take<uint8_t>(nch);
-  double *xh = cv.take<double>(nch);
   int32_t *spe = cv.take<int32_t>(nch * 2);
   long long *spd = cv.take<long long>(nch * 6);
   int32_t *spa = cv.take<int32_t>(nch * 2);
@@ -4204,7 +4246,6 @@ Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const 
   uint8_t *ssel = cv.take<uint8_t>(nch);  // Summ::sel
   double2 *tagg = cv.take<double2>(ntiles);
   double *tin = cv.take<double>(ntiles);
-  int32_t *trun = cv.take<int32_t>(ntiles + 1);
   const int64_t ngt = nch / 64 + 2;  // global 64-chunk tiles (carry tile batches)
   int32_t *gte = cv.take<int32_t>(ngt);
   long long *gtd = cv.take<long long>(ngt * 6);
@@ -4219,11 +4260,10 @@ Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const 
 
   Work w{};
   if (!base) return w;
-  w.g = Chunks{start, n, run, nch, packed};
+  w.g = Chunks{kp.start, kp.n, kp.run, nch, packed};
   w.p1 = P1{p1d, p1d + nch, p1d + 2 * nch, p1d + 3 * nch, p1d + 4 * nch, p1d + 5 * nch, p1i, p1i + nch, spec,
             p1i + 2 * nch};
   w.p1.ep = ep;
-  w.xt = xt;
   w.sm = Summ{se, sD, sD + 2 * nch, sD + 4 * nch, sA};
   w.cr = Carry{x, cmode, hq, hmax, hq + nch};
   w.cnts = cnts;
@@ -4238,13 +4278,12 @@ Work carve(char *base, const ScanPlan &plan, int64_t nch, int64_t ntiles, const 
   w.pa = pa;
   w.pb = pb;
   w.pz = pz;
-  w.xh = xh;
   w.sp1 = SummP1{spe, spd, spd + 2 * nch, spd + 4 * nch, spa};
   w.nfix = nfix;
   w.fix = reinterpret_cast<int64_t *>(nfix + 2);
   w.tagg = tagg;
   w.tin = tin;
-  w.trun = trun;
+  w.trun = kp.trun;
   w.tcomp = TileComp{gte, gtd, gtd + 2 * ngt, gtd + 4 * ngt, gtm, gtee};
   // (the carry reads no replay slots unless k_marks_select wrote them)
   w.rpb = ReplayBuf{plan.p1summ ? rslot : nullptr, rchunk, rval, rcnt, rcap_h};
@@ -4576,6 +4615,11 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   hipStream_t st = ctx->stream, side = ctx->side, hi = ctx->hi;
   const int64_t nruns = runs.n, nch = lay.nch, ntiles = lay.ntiles;
   ctx->chunked_events = false;
+  // The kept slot's tag (what the previous chunked scan on this context left
+  // for this one) is taken and cleared here and set again where the call
+  // returns KS_OK, so a failed call or a retry leaves none behind.
+  const ChunkKeep prev = ctx->chunk_keep;
+  chunk_keep_clear(ctx);
   if (nruns == 0 || nch == 0) return KS_OK;
   const EmitCfg ec{mode.trlr, mw, min_score, mode.min_len, mode.ks, k};
   const ScanCall c{ctx, s, s->offsets_host[s->nseq], k, tv, ec, runs, lay, rb, visits, visits_rescan, mode};
@@ -4589,12 +4633,29 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
     return KS_OK;
   };
 
+  // ---- the kept slot.  A matching tag implies a sequence index hit with the
+  // cached layout: a build or a new layout clears it (find_runs, run_layout).
+  size_t kbytes = 0;
+  carve_keep(nullptr, nch, ntiles, &kbytes);
+  void *ksp = nullptr;
+  KS_TRY(ensure(ctx, SLOT_CHUNK_KEEP, kbytes, &ksp));
+  const Keep kp = carve_keep(static_cast<char *>(ksp), nch, ntiles, &kbytes);
+  const uint64_t ixid = mode.index ? mode.index->id : 0;
+  const bool kept = ixid != 0 && prev.id == ixid && prev.k == k && prev.trlr == mode.trlr && prev.nch == nch &&
+                    prev.ntiles == ntiles && prev.base == ksp;
+  const bool chunk_reuse = kept && getenv("KS_NO_CHUNK_REUSE") == nullptr;
+  const bool hint_reuse = kept && plan.p1summ && prev.hint >= 0 && prev.table_id == mode.table_id &&
+                          prev.init_id == mode.init_id && getenv("KS_NO_ENTRY_HINT") == nullptr;
+
   // ---- workspace
   size_t bytes = 0;
-  carve(nullptr, plan, nch, ntiles, runs.packed, &bytes);
+  carve(nullptr, plan, nch, ntiles, runs.packed, kp, &bytes);
   void *wsp = nullptr;
   KS_TRY(ensure(ctx, SLOT_CHUNK_A, bytes, &wsp));
-  Work w = carve(static_cast<char *>(wsp), plan, nch, ntiles, runs.packed, &bytes);
+  Work w = carve(static_cast<char *>(wsp), plan, nch, ntiles, runs.packed, kp, &bytes);
+  const int hx = hint_reuse ? prev.hint : 0;  // the array pass 1 reads; P2 writes the other
+  w.xh = kp.hint[hx];
+  w.xt = kp.hint[1 - hx];
   w.p1.epoch = ++ctx->scan_epoch;
   unsigned long long *cnts = w.cnts;
   KS_HIP(hipMemsetAsync(cnts, 0, 8 * (2 * kSegs + 8), st));
@@ -4633,12 +4694,25 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
 
   // ---- P0 chunk layout, predictor
   KS_TRY(record(kEvBegin, st));
-  KS_TRY(launch(k_tile_runs, dim3((unsigned)nruns), dim3(256), 0, st, lay.tbase, nruns, w.trun));
-  if (ntiles > 0)
-    KS_TRY(launch(k_make_chunks, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, runs.a, lay.cbase, lay.tbase,
-                  w.trun, ntiles, k, runs.b, mode.trlr, w.g));
+  if (!chunk_reuse) {
+    KS_TRY(launch(k_tile_runs, dim3((unsigned)nruns), dim3(256), 0, st, lay.tbase, nruns, w.trun));
+    if (ntiles > 0)
+      KS_TRY(launch(k_make_chunks, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, runs.a, lay.cbase,
+                    lay.tbase, w.trun, ntiles, k, runs.b, mode.trlr, w.g));
+  }
   bool side_forked = false;  // the side stream already waits for the chunks
-  if (plan.p1summ) {
+  if (hint_reuse) {
+    // no predictor: w.xh is the previous call's P2 prediction (from pass 1's
+    // exact clean exits and sums, closer than P0's); both parts' pass 1 read it
+    if (const char *th = getenv("KS_TEST_ENTRY_HINT")) {
+      const int what = !strcmp(th, "zero") ? 0 : !strcmp(th, "huge") ? 1 : !strcmp(th, "nan") ? 2 :
+                       !strcmp(th, "shift") ? 3 : -1;
+      if (what < 0) return fail(KS_ERR_ARG, "KS_TEST_ENTRY_HINT must be zero, huge, nan or shift");
+      // (w.pa, the predictor's sums, is free on this path: the copy the shift reads)
+      if (what == 3) KS_HIP(hipMemcpyAsync(w.pa, w.xh, (size_t)nch * 8, hipMemcpyDeviceToDevice, st));
+      KS_TRY(launch(k_test_hint, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, w.xh, w.pa, nch, what));
+    }
+  } else if (plan.p1summ) {
     // the first half's predictor and prescan first (they gate its pass 1;
     // the predictor holds whole CUs: 128 KiB of LDS per block), then the
     // second half's on the side stream, under the first half's pass 1 (also
@@ -4770,6 +4844,15 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
     stats->n_replay = (int64_t)replays;
   }
   ctx->chunked_events = true;
+  if (ixid != 0) {
+    // what this call leaves for the next one: the chunk table, and w.xt, which
+    // P2 wrote for every chunk (ascan covers every run and tile of both parts)
+    ctx->chunk_keep = ChunkKeep{ixid, k, mode.trlr, nch, ntiles, ksp, mode.table_id, mode.init_id, 1 - hx};
+    ks_seq_index *ix = mode.index;
+    if (chunk_reuse) ++ix->chunk_reuses;
+    if (hint_reuse) ++ix->hint_reuses;
+    if (plan.p1summ && !hint_reuse) ++ix->predictor_builds;
+  }
   return KS_OK;
 }
 

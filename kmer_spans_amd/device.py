@@ -28,10 +28,19 @@ class SeqIndex:
         self._h = C.c_void_p()
         check(load().ks_seq_index_create(C.byref(s), C.byref(self._h)))
 
-    def info(self) -> dict:
+    def _info(self) -> _lib.SeqIndexInfo:
         inf = _lib.SeqIndexInfo()
         check(load().ks_seq_index_info_get(self._h, C.byref(inf)))
-        return inf.as_dict()
+        return inf
+
+    def info(self) -> dict:
+        """The index's own counters: builds, hits, layout_builds, guard_failures."""
+        return self._info().as_dict(_lib.SeqIndexInfo.INDEX_FIELDS)
+
+    def scan_info(self) -> dict:
+        """What the chunked scans with this index took from the previous scan:
+        chunk_reuses, hint_reuses, predictor_builds (ks_seq_index_info)."""
+        return self._info().as_dict(_lib.SeqIndexInfo.SCAN_FIELDS)
 
     def close(self):
         if self._h:
