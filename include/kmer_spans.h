@@ -885,6 +885,124 @@ ks_status ks_nj(ks_ctx *ctx, const double *diss, int64_t n, int32_t *join, doubl
 ks_status ks_nj_edges(const int32_t *join, const double *length, const int32_t *root, const double *root_length,
                       int64_t n, int32_t *edge, double *edge_length);
 
+/* ---------------------------------------------------------------------
+ * Principal components of region spectra (csrc/ks_pca.hip).
+ * --------------------------------------------------------------------- */
+
+/* The other thing the reference's author does with the spectra (test.R:734-736
+ * prcomp(x, center=FALSE) of every spectra matrix, "but this is really slow!!";
+ * :811 prcomp of the high-entropy subset, centred): the principal components
+ * of the row-normalised profiles -- without taking the counts to the host.
+ *
+ * Input: a spectra matrix as ks_region_spectra_dev writes it, n x ncol uint32,
+ * row-major, and an optional int64 row selection as in ks_spectra_dist_dev
+ * (any order, repeats allowed; NULL with a count of m means rows 0 .. m - 1,
+ * m > n is an error then).  m >= 2.  1 <= ncol <= KS_PCA_MAX_NCOL (q <= 5);
+ * 1 <= ncomp <= ncol.  Row s below is position s of the selection.
+ * Profile: p[s][c] = (double)cnt / (double)T, T the row sum in 64-bit integers,
+ * one IEEE division: the profile of ks_spectra_dist.  A selected row with
+ * T = 0 has no profile: KS_ERR_ARG, "row s has no counts", s the first such
+ * position.  A bad row index is KS_ERR_ARG, "row index s out of range", s the
+ * first such position, and is reported before an empty row.
+ * Centre: acc = 0; for s = 0 .. m - 1 ascending: acc = acc + p[s][c];
+ * center[c] = acc / (double)m; xc[s][c] = p[s][c] - center[c].  With
+ * KS_PCA_NO_CENTER (R's center=FALSE) center is written as zeros and xc = p.
+ * Cross-product: G[a][b]: acc = 0; for s ascending: acc = acc + xc[s][a] *
+ * xc[s][b], the multiplication and the addition separate FP64 operations (no
+ * FMA), one accumulator per entry.  G[a][b] and G[b][a] carry the same bits.
+ * So center and G can be predicted bit for bit by a host loop.
+ *
+ * Eigen-decomposition of G: cyclic two-sided Jacobi in the round-robin
+ * (tournament) order.  P = ncol rounded up to even; index P - 1 is a dummy
+ * when ncol is odd.  A sweep is the rounds r = 0 .. P - 2; round r holds the
+ * P / 2 disjoint pairs of slot 0: (P - 1, r) and slot i = 1 .. P / 2 - 1:
+ * ((r + i) mod (P - 1), (r - i) mod (P - 1)), each taken as (p, q) with p < q;
+ * the pair holding the dummy is skipped.  (ks_pca_round_pairs lists them.)
+ * State: A = G, V = I, floor = 2^-52 * max over c of |G[c][c]|.  For a pair, with
+ * app = A[p][p], aqq = A[q][q], apq = A[p][q] read before the round:
+ *   skip rule: the pair is skipped (c = 1, s = 0) unless |apq| > floor and
+ *     apq * apq > 2^-104 * |app * aqq|.  The second is the usual test relative to
+ *     sqrt(|app aqq|); the floor stops the rotation of rounding noise among
+ *     the (near-)zero eigenvalues that centring, duplicate columns (column c of
+ *     a both-strands spectrum equals column rc(c)), all-zero columns and
+ *     m <= ncol leave, where the relative test alone never tires.  An all-zero
+ *     G has floor = 0 and every pair is skipped;
+ *   rotation: theta = (aqq - app) / (2 apq);
+ *     t = 1 / (|theta| + sqrt(theta * theta + 1)), negated if theta < 0
+ *     (theta = 0, the duplicate-column case, gives t = 1);
+ *     c = 1 / sqrt(t * t + 1);  s = t * c.
+ * All the round's rotations J (J[p][p] = J[q][q] = c, J[p][q] = s, J[q][p] =
+ * -s) are applied at once, A <- J^T A J and V <- V J: an entry A[i][j] with i in
+ * pair k1 and j in pair k2 (slots k1 < k2) first takes pair k2's column step
+ *   (x_ip, x_iq) <- (c x_ip - s x_iq, s x_ip + c x_iq),
+ * then pair k1's row step of the same form, and is stored at [i][j] and [j][i]
+ * (A stays symmetric in bits); a pair's own block is set in closed form, A[p][p]
+ * = app - t apq, A[q][q] = aqq + t apq, A[p][q] = A[q][p] = 0; V's columns p and
+ * q take the column step.  A block or a row of V none of whose pairs rotates is
+ * left as it is.
+ * Termination: the loop ends with the first sweep in which no pair is rotated
+ * (n_sweeps counts that sweep too: an all-zero G ends with n_sweeps = 1,
+ * n_rotations = 0).  Every rotation removes 2 apq^2 > 2 floor^2 from the
+ * off-diagonal norm, so the loop ends; more than KS_PCA_MAX_SWEEPS sweeps is
+ * KS_ERR_INTERNAL.  lambda[j] = A[j][j], its vector is column j of V.  This
+ * stage uses sqrt and division: its bits are not promised, its error is
+ * (DESIGN.md 6k).
+ * Order and sign: components by lambda descending, equal values in Jacobi
+ * column order.  Each loading vector is negated if needed so that its entry
+ * of largest absolute value is positive; among equal absolute values the
+ * lowest index decides.
+ *
+ * Outputs:
+ *   center   ncol doubles.
+ *   sdev     ncol doubles, sdev[j] = sqrt(max(lambda_j, 0) / (double)(m - 1)):
+ *            R's sdev (prcomp divides by m - 1 without centring too).
+ *   rotation ncol x ncomp doubles, row-major: component j is column j.  The
+ *            first k columns of any call are the bits of the first k columns
+ *            of the full call (ncomp = ncol).
+ *   x        m x ncomp doubles, row-major, may be NULL: the scores, x[s][j]:
+ *            acc = 0; for c = 0 .. ncol - 1 ascending: acc = acc + xc[s][c] *
+ *            rotation[c][j], separate operations, one accumulator per entry:
+ *            predictable bit for bit from the returned center and rotation.
+ *   gram     ncol x ncol doubles, may be NULL: G.
+ * The result is a function of the input alone, with the same bits on every
+ * run: no atomics on doubles, no reduction that depends on arrival order.
+ * ctx == NULL is the default context on device 0; the calls are never spread
+ * over a device list and are not forwarded by the fork broker. */
+#define KS_PCA_MAX_NCOL 1024
+#define KS_PCA_MAX_SWEEPS 64
+#define KS_PCA_NO_CENTER 1
+typedef struct ks_pca_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total;
+  double ms_normalise; /* check, profiles, centre */
+  double ms_gram;
+  double ms_eigen;     /* Jacobi (its read-backs included), order and sign */
+  double ms_project;
+  int64_t n_sweeps;
+  int64_t n_rotations;
+  int64_t panel_bytes; /* device memory the call allocated and freed: the m x ncol FP64 panel and three P x P matrices */
+} ks_pca_stats;
+
+/* Device-resident: spectra_dev, rows_dev and the five outputs are device
+ * pointers.  Indices and row sums are checked on the device before any output
+ * is written: after a rejected call the outputs are untouched and the context
+ * usable.  The only allocation is the work memory counted in panel_bytes
+ * (KS_ERR_NOMEM if it fails), freed before return.  All other arguments are
+ * validated before any device call.  stats may be NULL. */
+ks_status ks_spectra_pca_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                             const int64_t *rows_dev, int64_t m, int32_t flags, int32_t ncomp, double *center_dev,
+                             double *sdev_dev, double *rotation_dev, double *x_dev, double *gram_dev,
+                             ks_pca_stats *stats);
+/* Host buffers: validates every argument, every index and every row sum
+ * before any device call, then uploads, runs the device entry and copies the
+ * results back. */
+ks_status ks_spectra_pca(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                         int64_t m, int32_t flags, int32_t ncomp, double *center, double *sdev, double *rotation,
+                         double *x, double *gram);
+/* The Jacobi schedule on the host: the pairs of round `round` (0 .. P - 2) of
+ * ncol columns in slot order, p[i] < q[i], the dummy's pair left out; p and q
+ * hold P / 2 entries.  Returns the pair count, -1 for a bad argument. */
+int32_t ks_pca_round_pairs(int32_t ncol, int32_t round, int32_t *p, int32_t *q);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

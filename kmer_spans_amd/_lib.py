@@ -117,6 +117,15 @@ class NjStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class PcaStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_gram", C.c_double),
+                ("ms_eigen", C.c_double), ("ms_project", C.c_double), ("n_sweeps", C.c_int64),
+                ("n_rotations", C.c_int64), ("panel_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -153,6 +162,7 @@ EXPORTS = [
     "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
     "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
     "ks_nj", "ks_nj_dev", "ks_nj_edges",
+    "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
     "ks_scan_chunk_indices", "ks_scan_tile_chunks",
@@ -166,6 +176,9 @@ HCLUST_METHODS = {"complete": 0, "single": 1, "average": 2}  # KS_HCLUST_*
 KS_HCLUST_KEEP_INPUT = 1
 KS_NJ_KEEP_INPUT = 1
 KS_NJ_NO_COMPACT = 2
+KS_PCA_MAX_NCOL = 1024
+KS_PCA_MAX_SWEEPS = 64
+KS_PCA_NO_CENTER = 1
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -250,6 +263,9 @@ def load():
         "ks_nj": ([P, P, I64, P, P, P, P], I32),
         "ks_nj_dev": ([P, P, I64, I32, P, P, P, P, P], I32),
         "ks_nj_edges": ([P, P, P, P, I64, P, P], I32),
+        "ks_spectra_pca": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P], I32),
+        "ks_spectra_pca_dev": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P, P], I32),
+        "ks_pca_round_pairs": ([I32, I32, P, P], I32),
         "ks_seq_index_create": ([P, P], I32),
         "ks_seq_index_destroy": ([P], None),
         "ks_seq_index_info_get": ([P, P], I32),

@@ -282,6 +282,44 @@ def region_distances(counts, rows=None, rows_b=None, squared: bool = False, devi
     return out
 
 
+def region_pca(counts, rows=None, center: bool = True, ncomp=None, scores: bool = True, device: int = 0) -> dict:
+    """Principal components of row-normalised spectra (R's prcomp() on
+    reg.kmer.sp, test.R:734-736 and :811) from the counts region_spectra
+    returns, computed on the device.
+
+    counts: [n, ncol] non-negative integers (uint32 range), 1 <= ncol <= 1024
+    (q <= 5).  rows: optional integer row indices (any order, repeats allowed;
+    at least 2 rows); None = all rows.  A row's profile is counts / row sum; a
+    selected row without counts is an error naming its position.  center=False
+    is prcomp's center=FALSE.  ncomp: components kept (default all ncol).
+    Returns {'sdev': float64[ncol] (R's sdev, over m - 1), 'rotation':
+    float64[ncol, ncomp] (loadings, columns by descending variance, each with
+    its largest entry positive), 'center': float64[ncol] (zeros when not
+    centred), 'x': float64[m, ncomp] scores, or None with scores=False}.  The
+    centre and the scores are fixed orders of FP64 operations
+    (include/kmer_spans.h); the same input gives the same bits on every run."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "iu":
+        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
+    if c.dtype != np.uint32:
+        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+            raise KmerSpansError("counts must be in the uint32 range")
+        c = c.astype(np.uint32)
+    c = np.ascontiguousarray(c)
+    n, ncol = (int(v) for v in c.shape)
+    r = _rows_arg(rows, "rows")
+    m = n if r is None else int(r.size)
+    k = ncol if ncomp is None else int(ncomp)
+    kk = max(0, min(k, ncol))  # a bad ncomp is the library's error; the buffers only need a size
+    cen, sdev = np.zeros(ncol, dtype=np.float64), np.zeros(ncol, dtype=np.float64)
+    rot = np.zeros((ncol, kk), dtype=np.float64)
+    x = np.zeros((max(m, 0), kk), dtype=np.float64) if scores else None
+    check(load().ks_spectra_pca(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None, m,
+                                0 if center else _lib.KS_PCA_NO_CENTER, k, cen.ctypes.data, sdev.ctypes.data,
+                                rot.ctypes.data, x.ctypes.data if x is not None else None, None))
+    return {"sdev": sdev, "rotation": rot, "center": cen, "x": x}
+
+
 def region_hclust(dist, method: str = "complete", device: int = 0) -> dict:
     """R's hclust() of a condensed dissimilarity vector (test.R:776), run on
     the device.

@@ -598,3 +598,42 @@ def region_nj(ctx: _lib.Context, dist: torch.Tensor, keep_input: bool = True, co
                            join.ctypes.data, length.ctypes.data, root.ctypes.data, root_length.ctypes.data,
                            C.byref(st)))
     return {"join": join, "length": length, "root": root, "root_length": root_length}, st.as_dict()
+
+
+def region_pca(ctx: _lib.Context, counts: torch.Tensor, rows=None, center: bool = True, ncomp=None,
+               scores: bool = True, gram: bool = False):
+    """ks_spectra_pca_dev: principal components (R's prcomp, test.R:734-736,
+    :811) of the row-normalised spectra of region_spectra, on the device.
+
+    counts: the int32 CUDA tensor [n, ncol] region_spectra returns (uint32
+    bits), used in place; 1 <= ncol <= 1024.  rows: an optional selection of
+    row indices, an int64 CUDA tensor (used in place) or numpy (uploaded); any
+    order, repeats allowed, at least 2; None = all rows.  A selected row
+    without counts or a bad index is an error naming its position, and nothing
+    is written then.  center=False is prcomp's center=FALSE.  ncomp: components
+    kept (default ncol).  Returns (res, stats): res is a dict of float64 CUDA
+    tensors 'sdev' [ncol], 'rotation' [ncol, ncomp], 'center' [ncol], 'x'
+    [m, ncomp] (None with scores=False) and, with gram=True, 'G' [ncol, ncol],
+    the cross-product matrix of the (centred) profiles; stats the dict of
+    ks_pca_stats."""
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
+            or counts.dim() != 2 or not counts.is_contiguous()):
+        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
+    dev = counts.device
+    n, ncol = int(counts.shape[0]), int(counts.shape[1])
+    r = _rows_dev(rows, "rows", dev) if rows is not None else None
+    m = n if r is None else int(r.numel())
+    k = ncol if ncomp is None else int(ncomp)
+    kk = max(0, min(k, ncol))  # a bad ncomp is the library's error; the buffers only need a size
+    new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    res = {"sdev": new(ncol), "rotation": new(ncol, kk), "center": new(ncol), "x": new(m, kk) if scores else None}
+    if gram:
+        res["G"] = new(ncol, ncol)
+    st = _lib.PcaStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    _order(ctx)
+    check(load().ks_spectra_pca_dev(ctx.handle, C.c_void_p(counts.data_ptr()), n, ncol,
+                                    ptr(r), m, 0 if center else _lib.KS_PCA_NO_CENTER, k, ptr(res["center"]),
+                                    ptr(res["sdev"]), ptr(res["rotation"]), ptr(res["x"]), ptr(res.get("G")),
+                                    C.byref(st)))
+    return res, st.as_dict()
