@@ -433,7 +433,19 @@ ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, const ks
  * never by address.  A hint is only a hint: a wrong one costs gathered
  * summaries or replays (ks_scan_stats.n_replay may differ from a scan without
  * it), never a region, a score or a visit count.  KS_NO_CHUNK_REUSE=1 and
- * KS_NO_ENTRY_HINT=1 (read per call) switch either off. */
+ * KS_NO_ENTRY_HINT=1 (read per call) switch either off.
+ *
+ * On the wide-line and uint16-line table forms the slot also keeps the exact
+ * value every chunk was entered with.  The next scan with the same table(s)
+ * starts each chunk's pass 1 from it, walks the carried head itself and checks,
+ * bit for bit, that its exact exit is the kept entry of the next chunk of the
+ * run; a run's first chunk enters at 0, so when every check passes every kept
+ * entry is proved exact and the predictor, the summaries, the carry and the
+ * heads are not run at all (ks_seq_index_entry_info: entry_reuses; such a call
+ * also counts as a hint_reuses).  A failed check reruns the call on the hint
+ * path (entry_fallbacks).  The thresholds and the visit histogram are not part
+ * of the key: every index is scored and every excursion emitted under the
+ * call's own.  KS_NO_EXACT_ENTRY=1 (read per call) switches it off. */
 typedef struct ks_seq_index ks_seq_index;
 ks_status ks_seq_index_create(const ks_dev_seqs *seqs, ks_seq_index **out);
 void ks_seq_index_destroy(ks_seq_index *ix);
@@ -449,6 +461,10 @@ typedef struct ks_seq_index_info {
   int64_t predictor_builds; /* ran the predictor (pass-1-summary tables only)       */
 } ks_seq_index_info;
 ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_info *out);
+/* Chunked scans with the handle that started pass 1 from the kept exact
+ * entries and verified them (entry_reuses), and calls whose verification
+ * failed and that were rerun on the hint path (entry_fallbacks). */
+ks_status ks_seq_index_entry_info(const ks_seq_index *ix, int64_t *entry_reuses, int64_t *entry_fallbacks);
 ks_status ks_scan_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *seqs, ks_seq_index *ix, int32_t k,
                               const ks_table *table, int32_t min_width, double min_score, int32_t *visits_dev,
                               ks_regions *out, ks_scan_stats *stats);

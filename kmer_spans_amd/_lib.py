@@ -163,7 +163,7 @@ EXPORTS = [
     "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
     "ks_nj", "ks_nj_dev", "ks_nj_edges",
     "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
-    "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get",
+    "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
     "ks_scan_chunk_indices", "ks_scan_tile_chunks",
 ]

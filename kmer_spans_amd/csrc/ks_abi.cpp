@@ -751,6 +751,13 @@ extern "C" ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_
   return KS_OK;
 }
 
+extern "C" ks_status ks_seq_index_entry_info(const ks_seq_index *ix, int64_t *entry_reuses, int64_t *entry_fallbacks) {
+  if (!ix || !entry_reuses || !entry_fallbacks) return fail(KS_ERR_ARG, "null argument");
+  *entry_reuses = ix->entry_reuses;
+  *entry_fallbacks = ix->entry_fallbacks;
+  return KS_OK;
+}
+
 // The index of an _indexed call: nullptr (a plain call) without a handle or
 // under KS_NO_SEQ_INDEX (read per call); KS_ERR_ARG when seqs is not what the
 // handle was created for.

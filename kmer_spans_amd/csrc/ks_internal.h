@@ -137,7 +137,9 @@ struct SeqCache {
 // sequence index (only scan_chunked writes that slot): the chunk table
 // (Chunks::start / n / run) and the tile map (Work::trun), which depend on
 // the cached runs and layout, k and trlr only, and the entry hint, P2's
-// predicted entries of that call (Work::xt), which depend on the table(s)
+// predicted entries of that call (Work::xt), and the exact entries
+// (Carry::x, written in place by the general path's carry and verified, not
+// written, by a pass 1 that starts from them), which depend on the table(s)
 // too.  id 0: nothing.  chunk_keep_clear is the only way the tag goes away:
 // with the sequence cache's tag (seq_cache_clear), where ensure regrows the
 // slot, and at the top of every scan_chunked call, which sets it again only
@@ -151,6 +153,9 @@ struct ChunkKeep {
   // and the first-k-mer table) and which of the two hint arrays holds it
   uint64_t table_id = 0, init_id = 0;
   int hint = -1;  // -1: none
+  // Keep::entry holds every chunk's exact entry under the hint's key: the call
+  // that set the tag wrote (general path) or verified (exact-entry path) all of them
+  bool entry_ok = false;
 };
 
 // Process-unique id of a score table (ks_table::id, never 0): a table
@@ -209,6 +214,9 @@ struct ks_seq_index {
   // chunked scans with this index that returned KS_OK: chunk table taken from the kept slot,
   // entry hint taken from it, predictor run (pass-1-summary path without a hint)
   int64_t chunk_reuses = 0, hint_reuses = 0, predictor_builds = 0;
+  // pass 1 started from the kept exact entries and verified them (no P2-P4); a verification
+  // failed and the call was rerun on the hint path (ks_seq_index_entry_info)
+  int64_t entry_reuses = 0, entry_fallbacks = 0;
 };
 
 struct ks_table {

@@ -856,8 +856,34 @@ __device__ __forceinline__ void p1_put(const P1 &o, int64_t c, double prev, doub
 // / fmax skip it; S > best is false at a close and while S stays 0 (best > 0
 // inside, >= 0 outside), so open | (S > best) is the chain; want is decide()'s
 // reg || res less start on both sides (pos_of: only a run's index 0 stays put).
-template <bool kSumm, bool kTrlr>
+//
+// kExact (never with kSumm): the lane starts from the chunk's exact entry hx.T
+// (the kept slot's, Keep::entry) instead of a prediction.  Beside the clean
+// trajectory it walks the carried head with head_step -- the serial replay's
+// and k_heads' arithmetic -- until its first clamp, writes the chunk's Carry
+// fields itself and checks its exact exit against the kept entry of the next
+// chunk (finish_exact).  No summaries and none of the aggregates that only
+// P2-P4 read (asum, pmin, pmax, parg, sabs).
+
+// The carried excursion of a chunk's head: its value T, its maximum hmax with
+// the first argmax harg, and hq, the index of its first clamp (-1: none yet).
+struct Head { double T, hmax; int harg, hq; };
+// Scan index i with value v: nothing moves past the chunk's n indices or
+// after the clamp.  (By value: passed by reference the heads kernels took 12 B
+// of scratch per lane.)
+__device__ __forceinline__ Head head_step(Head h, double v, int i, int n) {
+  if (i < n && h.hq < 0) {
+    const double t = h.T + v;
+    h.T = t > 0 ? t : 0.0;
+    if (h.T == 0.0) h.hq = i;
+    else if (h.T > h.hmax) { h.hmax = h.T; h.harg = i; }
+  }
+  return h;
+}
+
+template <bool kSumm, bool kTrlr, bool kExact = false>
 struct P1Lane {
+  static_assert(!(kSumm && kExact), "the exact-entry pass writes no summaries");
   int64_t start;
   int n, f0;
   double prev = 0.0, best = 0.0;
@@ -871,12 +897,20 @@ struct P1Lane {
   double smaxabs = 0.0;  // max |s| (the rounding of every step, both binades)
   int sarg = 0, sarg2 = 0;
   bool sbad = false, sbad2 = false;
+  Head hx{0.0, -1.0, 0, 0};  // kExact: the carried head (hq = 0 while there is none to walk)
+  bool hclean = true;        // kExact: entered at 0
 
-  // first: the chunk starts its run; xp: the predicted entry (0: no summaries)
+  // first: the chunk starts its run; xp: the predicted entry (0: no summaries),
+  // kExact: the exact entry (a run's first chunk enters at 0 whatever xp holds)
   __device__ __forceinline__ void init(int64_t st, int nn, bool first, bool live, double xp) {
     start = st;
     n = nn;
     f0 = first ? 0 : -1;
+    if (kExact) {
+      const double x = (first || !live) ? 0.0 : xp;
+      hclean = x == 0.0;
+      hx = Head{x, -1.0, 0, hclean ? 0 : -1};
+    }
     if (kSumm && live && xp >= kP1SumMin && xp < 1.0e15) {
       se = binade_of(xp);
       sC = 1.5 * ldexp(1.0, se);
@@ -893,11 +927,15 @@ struct P1Lane {
 
   // scan index i (< n) with value s
   __device__ __forceinline__ void step(double s, int i, const EmitCfg &ec, const Cand &cand) {
-    asum += s;
-    pmin = asum < pmin ? asum : pmin;
-    parg = asum > pmax ? i : parg;
-    pmax = asum > pmax ? asum : pmax;
-    sabs += fabs(s);
+    if (kExact) {
+      hx = head_step(hx, s, i, n);
+    } else {
+      asum += s;
+      pmin = asum < pmin ? asum : pmin;
+      parg = asum > pmax ? i : parg;
+      pmax = asum > pmax ? asum : pmax;
+      sabs += fabs(s);
+    }
     special |= !isfinite(s);
     if (kSumm && se != INT32_MIN) {
       const double r = (s + sC) - sC;
@@ -945,6 +983,34 @@ struct P1Lane {
       summ_put(sp, c, 1, se2, sbad2, smaxabs, scur2, smx2, smn2, sarg2);
     }
     p1_put(o, c, prev, asum, pmin, pmax, parg, sabs, special, beg, best, arg);
+  }
+
+  // kExact: what the stitch, k_candidates and the epoch guard read of chunk c
+  // (the clean exit, the trailing excursion, the epoch stamp; the carry's mode
+  // -- they only tell clean from not clean -- and head), and the proof: the
+  // chunk's exact exit, the head's value if it never clamped and else the clean
+  // exit, must be the kept entry xh[c + 1] of the next chunk of the run, bit for
+  // bit (error bit 64: scan_chunked reruns the call on the hint path).  g is
+  // the part's view: parts are cut at run boundaries, so a chunk's successor in
+  // its run is inside it.
+  __device__ __forceinline__ void finish_exact(int64_t c, const Chunks &g, const P1 &o, const Carry &cr,
+                                               const double *__restrict__ xh, unsigned int *__restrict__ err) {
+    o.cexit[c] = prev;
+    o.special[c] = special ? 1 : 0;
+    o.ep[c] = o.epoch;
+    if (prev > 0) {
+      o.tbeg[c] = beg; o.tmax[c] = best; o.targ[c] = arg;
+    } else {
+      o.tbeg[c] = -1; o.tmax[c] = 0.0; o.targ[c] = 0;
+    }
+    cr.mode[c] = (uint8_t)(hclean ? kModeClean : kModeU);
+    cr.hq[c] = hclean ? -1 : hx.hq;  // (clean: the values head_one writes)
+    cr.hmax[c] = hx.hmax;
+    cr.harg[c] = hx.harg;
+    const double ex = (hclean || hx.hq >= 0) ? prev : hx.T;
+    if (c + 1 < g.nch && g.run[c + 1] == g.run[c] &&
+        __double_as_longlong(ex) != __double_as_longlong(xh[c + 1]))
+      atomicOr(err, 64u);
   }
 };
 
@@ -1529,15 +1595,19 @@ struct LaneBases {
   }
 };
 
-template <int OWN, bool kF64, bool kLdsLut, bool kTrlr>
+// kExact (compressed lines): xh holds the kept exact entries, and the lane
+// writes the chunk's Carry fields and verifies its exit (P1Lane::finish_exact).
+template <int OWN, bool kF64, bool kLdsLut, bool kTrlr, bool kExact = false>
 __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t total, int k, TableView tv,
                                                               EmitCfg ec, uint32_t *__restrict__ visits, P1 o,
-                                                              Cand cand, const double *__restrict__ xh, SummP1 sp) {
+                                                              Cand cand, const double *__restrict__ xh, SummP1 sp,
+                                                              Carry cr, unsigned int *__restrict__ err) {
+  static_assert(!(kExact && kF64), "exact entries: compressed lines only");
   constexpr int BS = kF64 ? 1024 : 768;  // 16 / 12 waves: ring 128 / 96 KiB (+ the LUT)
   constexpr int LV = kF64 ? 1 : 2;
   constexpr int J = OWN + LV;
   constexpr int NS = (CH + J - 1) / J;  // steps per chunk (the same for the whole wave)
-  constexpr bool kSumm = true;  // (xh == nullptr: no predicted binades, no summaries)
+  constexpr bool kSumm = !kExact;  // (xh == nullptr: no predicted binades, no summaries)
   constexpr bool kLut = !kF64 && kLdsLut;
   static_assert(kF64 ? OWN + 4 <= 8 : OWN + 20 <= 32, "line layout");
   __shared__ __attribute__((aligned(16))) uint8_t s_ring[(BS / 64) * 2 * 4096];
@@ -1554,8 +1624,8 @@ __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t 
   const int n = live ? g.n[c] : 0;
   const bool first = live && (c == 0 || g.run[c - 1] != g.run[c]);
   const uint32_t kmask = (1u << (2 * k)) - 1u;
-  P1Lane<kSumm, kTrlr> L;
-  L.init(start, n, first, live, (kSumm && live && xh) ? xh[c] : 0.0);
+  P1Lane<kSumm, kTrlr, kExact> L;
+  L.init(start, n, first, live, (live && xh) ? xh[c] : 0.0);
   LaneBases B;
   B.load(g.packed, total, start - k);
   const int kx = k + J - 1;  // key length (<= 17)
@@ -1631,7 +1701,9 @@ __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t 
       }
     }
   }
-  if (live) L.finish(c, o, sp);
+  if (!live) return;
+  if constexpr (kExact) L.finish_exact(c, g, o, cr, xh, err);
+  else L.finish(c, o, sp);
 }
 
 // Pass 1 on a wide line table (line_kind 3, 128-B lines, k_build_line_wide):
@@ -1662,10 +1734,12 @@ __device__ __forceinline__ void glds4(const void *gsrc, uint32_t lds) {
                : "memory");
 }
 
-template <int OWN, bool kTrlr>
+// kExact: as k_pass1l's.
+template <int OWN, bool kTrlr, bool kExact = false>
 __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
                                                        uint32_t *__restrict__ visits, P1 o, Cand cand,
-                                                       const double *__restrict__ xh, SummP1 sp) {
+                                                       const double *__restrict__ xh, SummP1 sp, Carry cr,
+                                                       unsigned int *__restrict__ err) {
   constexpr int BS = kWideBlock;
   constexpr int J = OWN + 3;
   constexpr int NS = (CH + J - 1) / J;
@@ -1686,7 +1760,7 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
   const int n = live ? g.n[c] : 0;
   const bool first = live && (c == 0 || g.run[c - 1] != g.run[c]);
   const uint32_t kmask = (1u << (2 * k)) - 1u;
-  P1Lane<true, kTrlr> L;
+  P1Lane<!kExact, kTrlr, kExact> L;
   L.init(start, n, first, live, (live && xh) ? xh[c] : 0.0);
   LaneBases B;
   B.load(g.packed, total, start - k);
@@ -1803,7 +1877,9 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   process(NS - 1, vp, xp, ep);
-  if (live) L.finish(c, o, sp);
+  if (!live) return;
+  if constexpr (kExact) L.finish_exact(c, g, o, cr, xh, err);
+  else L.finish(c, o, sp);
 }
 
 // Pass 1 over weighted-rank code lines (ks_table::d_rlines, line kind 4):
@@ -3465,21 +3541,7 @@ __global__ void k_fallback_prep(unsigned int *__restrict__ err, unsigned long lo
 
 // ------------------------------------------------------------------- P4
 
-// The carried excursion of a chunk's head: its value T, its maximum hmax with
-// the first argmax harg, and hq, the index of its first clamp (-1: none yet).
-struct Head { double T, hmax; int harg, hq; };
-// Scan index i with value v: nothing moves past the chunk's n indices or
-// after the clamp.  (By value: passed by reference the heads kernels took 12 B
-// of scratch per lane.)
-__device__ __forceinline__ Head head_step(Head h, double v, int i, int n) {
-  if (i < n && h.hq < 0) {
-    const double t = h.T + v;
-    h.T = t > 0 ? t : 0.0;
-    if (h.T == 0.0) h.hq = i;
-    else if (h.T > h.hmax) { h.hmax = h.T; h.harg = i; }
-  }
-  return h;
-}
+// (Head and head_step: before P1Lane, whose exact-entry flavour walks the head too.)
 
 // Heads of the R chunks (the carried excursion up to its certain clamp):
 // lane per chunk, from the exact entry.  Uncompressed tables read the
@@ -3955,11 +4017,12 @@ __global__ void __launch_bounds__(256) k_test_hint(double *__restrict__ xh, cons
 
 // ------------------------------------------------------------ host driver
 //
-// scan_chunked reads top to bottom: plan (plan_scan: which path the call
-// takes) -> kept slot (carve_keep: what the previous scan left) -> workspace
-// (carve) -> layout kernels -> predictor (either only without it) -> pass 1 ->
-// post-processing and rescans per half -> counter read-back -> retry
-// decisions.  The helpers before it launch; none of them decides a path.
+// scan_chunked reads top to bottom: kept slot (carve_keep: what the previous
+// scan left) -> plan (plan_scan: which path the call takes, and what it takes
+// from the kept slot) -> workspace (carve) -> layout kernels -> predictor
+// (either only without it) -> pass 1 -> post-processing and rescans per half
+// -> counter read-back -> retry decisions.  The helpers before it launch; none
+// of them decides a path.
 namespace {
 
 // Slots of ks_ctx::ev this file records (chunked_phase_times reads the phase marks).
@@ -4079,11 +4142,25 @@ struct ScanPlan {
   int nhalf;
   Half half[2];
   bool debug_carry, debug_verify;  // KS_DEBUG_CARRY, KS_DEBUG_VERIFY (diagnostics; read once per process)
+  // What the call takes from the kept slot (kept: the previous chunked scan on
+  // the context was of the same sequence index, k, scan kind and layout, and
+  // the slot's buffer is still the one it wrote):
+  //  chunk_reuse: the chunk table and tile map (KS_NO_CHUNK_REUSE: off);
+  //  hint_reuse: with the same table(s), that scan's P2 prediction as the
+  //    entry hint, no predictor (KS_NO_ENTRY_HINT: off, and entry_reuse too);
+  //  entry_reuse: its exact entries (ChunkKeep::entry_ok).  Pass 1 starts from
+  //    them, writes the Carry fields and verifies every entry, and P2-P4 are
+  //    not run at all (KS_NO_EXACT_ENTRY: off, for A/B runs and tests).  On
+  //    the compressed line families' kernels (k_pass1w, k_pass1l); not with
+  //    the diagnostics that read P2-P4 results, nor with the forced fallback.
+  bool chunk_reuse, hint_reuse, entry_reuse;
 };
 
 // The plan of one call.  Reads every KS_* switch of this file (per call: tests
-// set them in-process between calls); makes no HIP call.
-ScanPlan plan_scan(const TableView &tv, int k, const ScanMode &mode, const Runs &runs, const RunLayout &lay) {
+// set them in-process between calls); makes no HIP call.  prev, kept: the kept
+// slot's tag and whether it matches this call (scan_chunked).
+ScanPlan plan_scan(const TableView &tv, int k, const ScanMode &mode, const Runs &runs, const RunLayout &lay,
+                   const ChunkKeep &prev, bool kept) {
   static const bool debug_carry = getenv("KS_DEBUG_CARRY") != nullptr;
   static const bool debug_verify = getenv("KS_DEBUG_VERIFY") != nullptr;
   const char *f64e = getenv("KS_F64_P1SUMM");
@@ -4133,6 +4210,12 @@ ScanPlan plan_scan(const TableView &tv, int k, const ScanMode &mode, const Runs 
   p.rank_alone = p.family == P1Family::F64Expanded && tv.rline && !mode.trlr && !p.p1summ && !p.split &&
                  (k == 14 || k == 15);
   p.tail = (p.family == P1Family::F64Expanded && !p.rank_alone) || p.family == P1Family::CompExpanded;
+
+  p.chunk_reuse = kept && getenv("KS_NO_CHUNK_REUSE") == nullptr;
+  p.hint_reuse = kept && p.p1summ && prev.hint >= 0 && prev.table_id == mode.table_id &&
+                 prev.init_id == mode.init_id && getenv("KS_NO_ENTRY_HINT") == nullptr;
+  p.entry_reuse = p.hint_reuse && prev.entry_ok && p.family == P1Family::Line && p.comp && !p.force_fb &&
+                  !p.debug_carry && !p.debug_verify && getenv("KS_NO_EXACT_ENTRY") == nullptr;
   return p;
 }
 
@@ -4162,6 +4245,12 @@ struct Keep {
   // call's xt writes the other array, so the roles swap from call to call and
   // P2 of the first part never overwrites what the second part's pass 1 reads
   double *hint[2];
+  // every chunk's exact entry: Work::cr.x of a scan with a sequence index, so
+  // the general path's carry (carry_segment, k_tile_apply, k_carry_exact: each
+  // writes cr.x of every live chunk it covers) leaves them here with no copy;
+  // a pass 1 from exact entries (ScanPlan::entry_reuse) reads and verifies
+  // them and writes none
+  double *entry;
 };
 
 Keep carve_keep(char *base, int64_t nch, int64_t ntiles, size_t *bytes) {
@@ -4173,6 +4262,7 @@ Keep carve_keep(char *base, int64_t nch, int64_t ntiles, size_t *bytes) {
   kp.trun = cv.take<int32_t>(ntiles + 1);
   kp.hint[0] = cv.take<double>(nch);
   kp.hint[1] = cv.take<double>(nch);
+  kp.entry = cv.take<double>(nch);
   *bytes = cv.off;
   return kp;
 }
@@ -4369,7 +4459,10 @@ ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, con
   const EmitCfg &ec = c.ec;
   const P1 &p1 = w.p1;
   const SummP1 &sp1 = w.sp1;
-  const double *xh = plan.p1summ ? w.xh : nullptr;
+  // (entry_reuse: the kept exact entries, Work::cr.x = Keep::entry, and the part's error bits)
+  const double *xh = plan.entry_reuse ? w.cr.x : (plan.p1summ ? w.xh : nullptr);
+  const Carry &cr = w.cr;
+  unsigned int *err = reinterpret_cast<unsigned int *>(w.cnts + 2 * kSegs + 2 * (&h - plan.half) + 1);
   const bool trlr = ec.trlr != 0;
   auto blocks = [&](int64_t per) { return dim3((unsigned)((n + per - 1) / per)); };
   auto persistent = [&](int per_cu) {
@@ -4395,22 +4488,28 @@ ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, con
       if (tv.line_kind == 3)  // wide lines: own 1..4 at k = 15..12 (J = 4..7)
         return pick_int<1, 3, 4>(own, [&](auto o) {
           return pick_bool(trlr, [&](auto t) {
-            return launch(k_pass1w<decltype(o)::value, decltype(t)::value>, blocks(kWideBlock), dim3(kWideBlock), 0,
-                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+            return pick_bool(plan.entry_reuse, [&](auto x) {
+              return launch(k_pass1w<decltype(o)::value, decltype(t)::value, decltype(x)::value>, blocks(kWideBlock),
+                            dim3(kWideBlock), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr, err);
+            });
           });
         });
       if (!plan.comp)
         return pick_int<3, 4, 2>(own, [&](auto o) {
           return pick_bool(trlr, [&](auto t) {
             return launch(k_pass1l<decltype(o)::value, true, false, decltype(t)::value>, blocks(1024), dim3(1024), 0,
-                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr, err);
           });
         });
       return pick_int<3, 5, 2>(own, [&](auto o) {
         return pick_bool(tv.nlut <= kLineLutMax, [&](auto l) {
           return pick_bool(trlr, [&](auto t) {
-            return launch(k_pass1l<decltype(o)::value, false, decltype(l)::value, decltype(t)::value>, blocks(768),
-                          dim3(768), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1);
+            return pick_bool(plan.entry_reuse, [&](auto x) {
+              return launch(k_pass1l<decltype(o)::value, false, decltype(l)::value, decltype(t)::value,
+                                     decltype(x)::value>,
+                            blocks(768), dim3(768), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr,
+                            err);
+            });
           });
         });
       });
@@ -4480,6 +4579,29 @@ ks_status post_half(const ScanCall &c, const ScanPlan &plan, const Work &w, int 
   unsigned int *err_h = reinterpret_cast<unsigned int *>(rep_h + 1);
   const dim3 gch_h((unsigned)((nh + 255) / 256)), gsum_h((unsigned)((nh + 1023) / 1024));
   const dim3 bw(64 * kWpb);
+  const dim3 gst((unsigned)((nt + kWpb - 1) / kWpb));
+  // P5 stitch
+  auto stitch = [&]() -> ks_status {
+    if (nt > 0)
+      KS_TRY(launch(k_stitch_tiles, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, p1, cr, w.xagg, h.t0,
+                    h.t1));
+    if (nr > 0)
+      KS_TRY(launch(k_stitch_runs, dim3((unsigned)nr), dim3(64), 0, strm, c.lay.tbase, h.r1, c.runs.a, c.runs.b,
+                    c.runs.seq, c.ec, w.xagg, w.xtin, c.rb, w.rss[hi], h.r0));
+    if (nt > 0)
+      KS_TRY(launch(k_stitch_emit, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, c.runs.a, c.runs.seq,
+                    p1, cr, c.ec, w.xtin, c.rb, w.rss[hi], err_h, h.t0, h.t1));
+    return KS_OK;
+  };
+  if (plan.entry_reuse) {
+    // pass 1 started from the exact entries and wrote the Carry fields: no
+    // P2-P4 (the phase marks stay, for chunked_phase_times)
+    if (last) {
+      KS_HIP(hipEventRecord(c.ctx->ev[kEvP2End], strm));
+      KS_HIP(hipEventRecord(c.ctx->ev[kEvP34End], strm));
+    }
+    return stitch();
+  }
   // ---- P2 prediction, segment starts, summaries
   KS_TRY(ascan(c, w, p1, w.xt, h, strm));
   const int64_t wl = (h.c0 > 0 ? h.c0 - 1 : 0) / 64;
@@ -4577,17 +4699,7 @@ ks_status post_half(const ScanCall &c, const ScanPlan &plan, const Work &w, int 
   if (last) KS_HIP(hipEventRecord(c.ctx->ev[kEvP34End], strm));
 
   // ---- P5 stitch
-  const dim3 gst((unsigned)((nt + kWpb - 1) / kWpb));
-  if (nt > 0)
-    KS_TRY(launch(k_stitch_tiles, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, p1, cr, w.xagg, h.t0,
-                  h.t1));
-  if (nr > 0)
-    KS_TRY(launch(k_stitch_runs, dim3((unsigned)nr), dim3(64), 0, strm, c.lay.tbase, h.r1, c.runs.a, c.runs.b,
-                  c.runs.seq, c.ec, w.xagg, w.xtin, c.rb, w.rss[hi], h.r0));
-  if (nt > 0)
-    KS_TRY(launch(k_stitch_emit, gst, bw, 0, strm, g, c.lay.tbase, c.lay.cbase, nruns, w.trun, c.runs.a, c.runs.seq,
-                  p1, cr, c.ec, w.xtin, c.rb, w.rss[hi], err_h, h.t0, h.t1));
-  return KS_OK;
+  return stitch();
 }
 
 // Candidates (count read on the device) and rescans of half h's lists on rst
@@ -4623,7 +4735,6 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   if (nruns == 0 || nch == 0) return KS_OK;
   const EmitCfg ec{mode.trlr, mw, min_score, mode.min_len, mode.ks, k};
   const ScanCall c{ctx, s, s->offsets_host[s->nseq], k, tv, ec, runs, lay, rb, visits, visits_rescan, mode};
-  const ScanPlan plan = plan_scan(tv, k, mode, runs, lay);
   auto record = [&](int e, hipStream_t strm) -> ks_status {
     KS_HIP(hipEventRecord(ctx->ev[e], strm));
     return KS_OK;
@@ -4643,9 +4754,8 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   const uint64_t ixid = mode.index ? mode.index->id : 0;
   const bool kept = ixid != 0 && prev.id == ixid && prev.k == k && prev.trlr == mode.trlr && prev.nch == nch &&
                     prev.ntiles == ntiles && prev.base == ksp;
-  const bool chunk_reuse = kept && getenv("KS_NO_CHUNK_REUSE") == nullptr;
-  const bool hint_reuse = kept && plan.p1summ && prev.hint >= 0 && prev.table_id == mode.table_id &&
-                          prev.init_id == mode.init_id && getenv("KS_NO_ENTRY_HINT") == nullptr;
+  const ScanPlan plan = plan_scan(tv, k, mode, runs, lay, prev, kept);
+  const bool chunk_reuse = plan.chunk_reuse, hint_reuse = plan.hint_reuse, entry_reuse = plan.entry_reuse;
 
   // ---- workspace
   size_t bytes = 0;
@@ -4656,6 +4766,9 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   const int hx = hint_reuse ? prev.hint : 0;  // the array pass 1 reads; P2 writes the other
   w.xh = kp.hint[hx];
   w.xt = kp.hint[1 - hx];
+  // with a sequence index the exact entries live in the kept slot: the carry
+  // leaves them there for the next scan (entry_reuse: pass 1 reads them there)
+  if (ixid != 0) w.cr.x = kp.entry;
   w.p1.epoch = ++ctx->scan_epoch;
   unsigned long long *cnts = w.cnts;
   KS_HIP(hipMemsetAsync(cnts, 0, 8 * (2 * kSegs + 8), st));
@@ -4704,13 +4817,17 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   if (hint_reuse) {
     // no predictor: w.xh is the previous call's P2 prediction (from pass 1's
     // exact clean exits and sums, closer than P0's); both parts' pass 1 read it
+    // (entry_reuse: they read the kept exact entries, w.cr.x, instead -- the
+    // array the test hook then spoils; the general path of the rerun rewrites
+    // every entry, so the slot is whole again afterwards)
     if (const char *th = getenv("KS_TEST_ENTRY_HINT")) {
       const int what = !strcmp(th, "zero") ? 0 : !strcmp(th, "huge") ? 1 : !strcmp(th, "nan") ? 2 :
                        !strcmp(th, "shift") ? 3 : -1;
       if (what < 0) return fail(KS_ERR_ARG, "KS_TEST_ENTRY_HINT must be zero, huge, nan or shift");
+      double *spoilt = entry_reuse ? w.cr.x : w.xh;
       // (w.pa, the predictor's sums, is free on this path: the copy the shift reads)
-      if (what == 3) KS_HIP(hipMemcpyAsync(w.pa, w.xh, (size_t)nch * 8, hipMemcpyDeviceToDevice, st));
-      KS_TRY(launch(k_test_hint, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, w.xh, w.pa, nch, what));
+      if (what == 3) KS_HIP(hipMemcpyAsync(w.pa, spoilt, (size_t)nch * 8, hipMemcpyDeviceToDevice, st));
+      KS_TRY(launch(k_test_hint, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, spoilt, w.pa, nch, what));
     }
   } else if (plan.p1summ) {
     // the first half's predictor and prescan first (they gate its pass 1;
@@ -4826,6 +4943,17 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   if (errbits & 32u)
     return fail(KS_ERR_DEVICE, "chunked scan epoch check failed: the stitch read pass-1 results not written by this "
                                  "call (epoch %u)", w.p1.epoch);
+  if (entry_reuse && (errbits & 64u)) {
+    // a kept entry was not the exact exit of the chunk before it: nothing of
+    // this attempt counts (scan_core resets the region counters and the
+    // scratch visit histogram per attempt).  The slot's chunk table and P2 hint
+    // were not written, so the tag goes back without entry_ok and the rerun
+    // takes the hint path, whose carry rewrites every entry.
+    ctx->chunk_keep = prev;
+    ctx->chunk_keep.entry_ok = false;
+    if (mode.index) ++mode.index->entry_fallbacks;
+    return KS_INTERNAL_RETRY;
+  }
   if (errbits & ~16u) return fail(KS_ERR_INTERNAL, "chunked scan consistency check failed (bits %u)", errbits);
   if ((int64_t)cand_max > csegcap) {  // grow the candidate buffers and rerun the pass
     void *grown = nullptr;
@@ -4846,11 +4974,16 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   ctx->chunked_events = true;
   if (ixid != 0) {
     // what this call leaves for the next one: the chunk table, and w.xt, which
-    // P2 wrote for every chunk (ascan covers every run and tile of both parts)
-    ctx->chunk_keep = ChunkKeep{ixid, k, mode.trlr, nch, ntiles, ksp, mode.table_id, mode.init_id, 1 - hx};
+    // P2 wrote for every chunk (ascan covers every run and tile of both parts);
+    // entry_reuse wrote neither, so the kept hint and its index pass on
+    // unchanged.  entry_ok: Work::cr.x is Keep::entry here, and the carry wrote
+    // every chunk's entry (general path) or pass 1 verified every one.
+    ctx->chunk_keep = ChunkKeep{ixid, k, mode.trlr, nch, ntiles, ksp, mode.table_id, mode.init_id,
+                                entry_reuse ? prev.hint : 1 - hx, true};
     ks_seq_index *ix = mode.index;
     if (chunk_reuse) ++ix->chunk_reuses;
     if (hint_reuse) ++ix->hint_reuses;
+    if (entry_reuse) ++ix->entry_reuses;
     if (plan.p1summ && !hint_reuse) ++ix->predictor_builds;
   }
   return KS_OK;

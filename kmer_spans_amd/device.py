@@ -42,6 +42,18 @@ class SeqIndex:
         chunk_reuses, hint_reuses, predictor_builds (ks_seq_index_info)."""
         return self._info().as_dict(_lib.SeqIndexInfo.SCAN_FIELDS)
 
+    def entry_info(self) -> dict:
+        """Scans that started pass 1 from the previous scan's exact chunk entries
+        and verified them (entry_reuses), and calls whose verification failed
+        and that were rerun on the hint path (entry_fallbacks)."""
+        # (typed here, not in _lib.load(): KS_LIB_PATH may name an earlier build, for A/B runs, without it)
+        fn = load().ks_seq_index_entry_info
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        fn.restype = C.c_int32
+        r, f = C.c_int64(), C.c_int64()
+        check(fn(self._h, C.byref(r), C.byref(f)))
+        return {"entry_reuses": int(r.value), "entry_fallbacks": int(f.value)}
+
     def close(self):
         if self._h:
             load().ks_seq_index_destroy(self._h)
