@@ -902,6 +902,95 @@ ks_status ks_nj_edges(const int32_t *join, const double *length, const int32_t *
                       int64_t n, int32_t *edge, double *edge_length);
 
 /* ---------------------------------------------------------------------
+ * Silhouette widths, medoids and diameters of a grouping
+ * (csrc/ks_silhouette.hip).
+ * --------------------------------------------------------------------- */
+
+/* What the reference author's script asks of the groups a tree cut gives
+ * (test.R:788-859: which height to cut at, which sequence represents a group,
+ * :791, how tight a group is, get.ph.groups' max.dist) -- without taking the
+ * matrix to the host: R's cluster::silhouette(cutree(hc, k), d), and with it
+ * each group's medoid and diameter.
+ *
+ * Inputs: diss, a condensed dissimilarity vector of n >= 2 observations as
+ * ks_spectra_dist_dev writes it (64-bit offsets).  Every entry must be finite,
+ * checked as for ks_hclust_dev and with its error text: KS_ERR_ARG,
+ * "dissimilarity at offset o is not finite", o the first such offset.  The
+ * vector is never modified.  group, a HOST int32[n] of labels in 1 .. ngroups
+ * as ks_hclust_cut writes it.  A label outside the range is KS_ERR_ARG,
+ * "group[i] = v is not in 1 .. g", i the first such index.  Empty groups are
+ * allowed (ngroups may exceed the largest label); fewer than two non-empty
+ * groups is KS_ERR_ARG.  The labels are checked on the host before any device
+ * call.
+ *
+ * Definitions, each a separate FP64 operation (no FMA), so that a short host
+ * loop reproduces every output bit for bit:
+ *   D(i, j) is the condensed entry of the pair (min, max); D(i, i) = +0.0 and
+ *   is added like any other entry, so that the chunk boundaries do not depend
+ *   on i.
+ *   Group sum.  The members of group c in ascending index order are cut into
+ *   chunks of KS_SIL_CHUNK consecutive members.  Chunk partial: P = +0.0, then
+ *   P = P + D(i, j) for each member j of the chunk, ascending.  S(i, c) = +0.0,
+ *   then S = S + P_q over the chunks q of c, ascending.  (The chunks give the
+ *   kernel n / 256 + g independent walks per row instead of g.)
+ *   Widths.  n_c is the size of group c, o the group of i.
+ *     a(i) = S(i, o) / (double)(n_o - 1), +0.0 when n_o == 1;
+ *     mean(i, c) = S(i, c) / (double)n_c for c != o with n_c > 0;
+ *     b(i) = the smallest such mean, scanning c ascending with a strict <, so
+ *     the lowest label wins a tie; neighbor[i] is that label;
+ *     width[i] = 0.0 when n_o == 1; otherwise (b - a) / b if a < b,
+ *     (b - a) / a if a > b, and 0.0 if neither holds (a definition of this
+ *     library for a == b, no claim about R).
+ *   Far.  far(i) = the largest D(i, j) over the members j of o, from +0.0 with
+ *   a strict >: exact in any order.
+ *   Per group c = 1 .. ngroups, at index c - 1: size = n_c; medoid = the
+ *   0-based member with the smallest S(i, c), ascending with a strict <, -1
+ *   for an empty group; diameter = the largest far over the members, from +0.0
+ *   with a strict >, NaN for an empty group; avg_width = the left-to-right sum
+ *   of width over the members, ascending from +0.0, divided by (double)n_c,
+ *   NaN for an empty group.
+ *   Overall.  avg_width_all = the left-to-right sum of width over all i,
+ *   ascending from +0.0, divided by (double)n.
+ * Everything that touches the matrix is device work; the O(n) per-group folds
+ * are host code on the per-row values.  With complete linkage and groups from
+ * ks_hclust_cut(h) every diameter is <= h. */
+#define KS_SIL_CHUNK 256
+typedef struct ks_silhouette_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total;  /* first check launch to the end of the widths kernel */
+  double ms_check;  /* the finiteness pass: one read of the matrix */
+  double ms_sums;   /* the chunked group sums, b, neighbor and far of every row */
+  double ms_widths; /* a and width of every row */
+  int64_t n;
+  int64_t ngroups;
+  int64_t n_chunks;   /* the sum over the groups of ceil(n_c / KS_SIL_CHUNK) */
+  int64_t work_bytes; /* device memory the call works in besides its arguments: the member list, the chunk table and
+                         the per-row values, 52 n + 8 n_chunks + 4 ngroups bytes and a few words, taken from the
+                         context workspace.  Nothing of size n x ngroups unless sums_dev is given. */
+} ks_silhouette_stats;
+
+/* diss_dev is a device pointer and is only read; group is a host pointer.
+ * Outputs are host pointers: width, a, b double[n]; neighbor int32[n]; size,
+ * medoid int32[ngroups]; diameter, avg_width double[ngroups]; avg_width_all
+ * one double.  sums_dev: an optional device buffer [n][ngroups] doubles,
+ * row-major, that receives S(i, c) at [i][c - 1] (+0.0 for an empty group);
+ * NULL for none.  flags must be 0.  All arguments are validated before any
+ * device call (n < 2, flag bits, null pointers, the labels).  If the work
+ * memory cannot be allocated the call fails with KS_ERR_NOMEM before anything
+ * is written on the device.  stats may be NULL.  ctx == NULL is the default
+ * context on device 0; the calls are never spread over a device list and are
+ * not forwarded by the fork broker. */
+ks_status ks_silhouette_dev(ks_ctx *ctx, const double *diss_dev, int64_t n, const int32_t *group, int32_t ngroups,
+                            int32_t flags, double *width, double *a, double *b, int32_t *neighbor, int32_t *size,
+                            int32_t *medoid, double *diameter, double *avg_width, double *avg_width_all,
+                            double *sums_dev, ks_silhouette_stats *stats);
+/* Host buffers: validates every argument and every entry before any device
+ * call, then uploads and runs the device entry on the upload.  sums: an
+ * optional host buffer [n][ngroups]. */
+ks_status ks_silhouette(ks_ctx *ctx, const double *diss, int64_t n, const int32_t *group, int32_t ngroups,
+                        int32_t flags, double *width, double *a, double *b, int32_t *neighbor, int32_t *size,
+                        int32_t *medoid, double *diameter, double *avg_width, double *avg_width_all, double *sums);
+
+/* ---------------------------------------------------------------------
  * Principal components of region spectra (csrc/ks_pca.hip).
  * --------------------------------------------------------------------- */
 

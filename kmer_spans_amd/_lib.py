@@ -117,6 +117,15 @@ class NjStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class SilhouetteStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_sums", C.c_double),
+                ("ms_widths", C.c_double), ("n", C.c_int64), ("ngroups", C.c_int64), ("n_chunks", C.c_int64),
+                ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class PcaStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_gram", C.c_double),
                 ("ms_eigen", C.c_double), ("ms_project", C.c_double), ("n_sweeps", C.c_int64),
@@ -162,6 +171,7 @@ EXPORTS = [
     "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
     "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
     "ks_nj", "ks_nj_dev", "ks_nj_edges",
+    "ks_silhouette", "ks_silhouette_dev",
     "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
@@ -176,6 +186,7 @@ HCLUST_METHODS = {"complete": 0, "single": 1, "average": 2}  # KS_HCLUST_*
 KS_HCLUST_KEEP_INPUT = 1
 KS_NJ_KEEP_INPUT = 1
 KS_NJ_NO_COMPACT = 2
+KS_SIL_CHUNK = 256
 KS_PCA_MAX_NCOL = 1024
 KS_PCA_MAX_SWEEPS = 64
 KS_PCA_NO_CENTER = 1
@@ -263,6 +274,8 @@ def load():
         "ks_nj": ([P, P, I64, P, P, P, P], I32),
         "ks_nj_dev": ([P, P, I64, I32, P, P, P, P, P], I32),
         "ks_nj_edges": ([P, P, P, P, I64, P, P], I32),
+        "ks_silhouette": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P], I32),
+        "ks_silhouette_dev": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P], I32),
         "ks_spectra_pca": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P], I32),
         "ks_spectra_pca_dev": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P, P], I32),
         "ks_pca_round_pairs": ([I32, I32, P, P], I32),
@@ -434,3 +447,33 @@ def nj_n(length: int) -> int:
 def nj_outputs(n: int):
     return (np.zeros((n - 3, 2), dtype=np.int32), np.zeros((n - 3, 2), dtype=np.float64),
             np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.float64))
+
+
+def silhouette_group(group, n: int, ngroups=None):
+    """(int32[n] labels, ngroups) of a group argument: ngroups defaults to the
+    largest label (the library checks the labels themselves)."""
+    g = np.asarray(group)
+    if g.ndim != 1 or g.dtype.kind not in "iu" or g.size != n:
+        raise KmerSpansError(f"group must hold one integer label for each of the {n} observations")
+    if g.size and (int(g.min()) < -0x80000000 or int(g.max()) > 0x7fffffff):
+        raise KmerSpansError("group labels must be in the int32 range")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    if ngroups is None:
+        ngroups = max(int(g.max()), 1)
+    elif int(ngroups) != ngroups or not 1 <= int(ngroups) <= 0x7fffffff:
+        raise KmerSpansError(f"ngroups = {ngroups} is not a positive int32")
+    return g, int(ngroups)
+
+
+def silhouette_outputs(n: int, ngroups: int) -> dict:
+    return {"width": np.zeros(n, dtype=np.float64), "a": np.zeros(n, dtype=np.float64),
+            "b": np.zeros(n, dtype=np.float64), "neighbor": np.zeros(n, dtype=np.int32),
+            "size": np.zeros(ngroups, dtype=np.int32), "medoid": np.zeros(ngroups, dtype=np.int32),
+            "diameter": np.zeros(ngroups, dtype=np.float64), "avg_width": np.zeros(ngroups, dtype=np.float64),
+            "avg_width_all": np.zeros(1, dtype=np.float64)}
+
+
+def silhouette_out_args(res: dict):
+    """The nine output pointers of ks_silhouette / ks_silhouette_dev, in order."""
+    return [res[k].ctypes.data for k in ("width", "a", "b", "neighbor", "size", "medoid", "diameter", "avg_width",
+                                         "avg_width_all")]

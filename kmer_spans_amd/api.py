@@ -401,6 +401,39 @@ def region_nj(dist, device: int = 0) -> dict:
     return {"join": join, "length": length, "root": root, "root_length": root_length}
 
 
+def region_silhouette(dist, group, ngroups=None, sums: bool = False, device: int = 0) -> dict:
+    """R's cluster::silhouette(cutree(hc, k), d) of a condensed dissimilarity
+    vector and a grouping of its observations, with each group's medoid and
+    diameter, run on the device.
+
+    dist: float64[n(n-1)/2], the condensed form region_distances returns; n >=
+    2 is solved from its length.  Every entry must be finite.  group: n integer
+    labels in 1 .. ngroups, as cut_tree returns them; ngroups defaults to the
+    largest label, groups without members are allowed, at least two must have
+    some.  Returns {'width', 'a', 'b': float64[n] (a the mean distance to the
+    own group, b to the nearest other one, width (b - a) / max(a, b), 0 for a
+    group of one), 'neighbor': int32[n] (the label of that nearest group),
+    'size', 'medoid': int32[g] (the 0-based member with the smallest sum of
+    distances to its group, -1 for an empty group), 'diameter', 'avg_width':
+    float64[g] (NaN for an empty group), 'avg_width_all': float}; with
+    sums=True also 'sums': float64[n, g], the sum of D(i, j) over the members j
+    of each group.  Every sum is a fixed order of FP64 additions
+    (include/kmer_spans.h): the same input gives the same bits on every run."""
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    if d.ndim != 1:
+        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
+    n = _lib.hclust_n(int(d.size))
+    g, ng = _lib.silhouette_group(group, n, ngroups)
+    res = _lib.silhouette_outputs(n, ng)
+    s = np.zeros((n, ng), dtype=np.float64) if sums else None
+    check(load().ks_silhouette(_ctx(device), d.ctypes.data, n, g.ctypes.data, ng, 0, *_lib.silhouette_out_args(res),
+                               s.ctypes.data if s is not None else None))
+    res["avg_width_all"] = float(res["avg_width_all"][0])
+    if sums:
+        res["sums"] = s
+    return res
+
+
 def _nj_tables(tree):
     """(join, length, root, root_length, n) of a region_nj tree, shapes checked."""
     join = np.ascontiguousarray(tree["join"], dtype=np.int32)

@@ -1,5 +1,5 @@
 // ks_finite_check.h -- the finiteness pass over a condensed dissimilarity
-// vector, shared by ks_hclust.hip and ks_nj.hip: the matrix is read once
+// vector, shared by ks_hclust.hip, ks_nj.hip and ks_silhouette.hip: the matrix is read once
 // (16-byte loads where the base allows, grid-stride) and the lowest offset of
 // a non-finite entry is kept with atomicMin; one 8-byte read-back ends a call
 // with a bad entry before anything is modified.  Include after ks_internal.h.

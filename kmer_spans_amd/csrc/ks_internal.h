@@ -84,7 +84,8 @@ constexpr int kScMultiWords = 104; // launch_count_multi: words per k of a batch
 constexpr int kScDistBad = 112;    // dist_impl: first bad row index of each selection [112, 114)
 constexpr int kScHclustBad = 114;  // hclust_impl: lowest offset of a non-finite dissimilarity
 constexpr int kScNjBad = 115;      // nj_impl: the same
-constexpr int kScEnd = 116;
+constexpr int kScSilBad = 116;     // sil_impl: the same
+constexpr int kScEnd = 117;
 
 struct DevBuf {
   void *ptr = nullptr;

@@ -612,6 +612,43 @@ def region_nj(ctx: _lib.Context, dist: torch.Tensor, keep_input: bool = True, co
     return {"join": join, "length": length, "root": root, "root_length": root_length}, st.as_dict()
 
 
+def region_silhouette(ctx: _lib.Context, dist: torch.Tensor, group, ngroups=None, sums: bool = False):
+    """ks_silhouette_dev: silhouette widths (R's cluster::silhouette), medoids
+    and diameters of the groups of cut_tree, from the condensed distances
+    region_distances returns, on the device.
+
+    dist: a contiguous float64 CUDA tensor of n(n-1)/2 entries, n >= 2, every
+    entry finite (a NaN from an empty spectrum row is an error naming its
+    offset); it is only read.  group: n integer labels in 1 .. ngroups as
+    cut_tree returns them, a numpy array or a tensor (a CUDA tensor is
+    downloaded, 4 n bytes); ngroups defaults to the largest label, groups
+    without members are allowed, at least two must have some.  Returns (res,
+    stats): res is a dict of numpy arrays 'width', 'a', 'b' float64 [n],
+    'neighbor' int32 [n], 'size', 'medoid' int32 [g], 'diameter', 'avg_width'
+    float64 [g] (medoid -1 and NaN for an empty group) and the float
+    'avg_width_all'; with sums=True also 'sums', a float64 CUDA tensor [n, g]
+    of the group sums S(i, c) (include/kmer_spans.h has the order of every
+    addition).  stats is the dict of ks_silhouette_stats."""
+    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
+            or not dist.is_contiguous()):
+        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
+    n = _lib.hclust_n(int(dist.numel()))
+    if isinstance(group, torch.Tensor):
+        group = group.detach().cpu().numpy()
+    g, ng = _lib.silhouette_group(group, n, ngroups)
+    res = _lib.silhouette_outputs(n, ng)
+    s = torch.empty((n, ng), dtype=torch.float64, device=dist.device) if sums else None
+    st = _lib.SilhouetteStats()
+    _order(ctx)
+    check(load().ks_silhouette_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n,
+                                   g.ctypes.data, ng, 0, *_lib.silhouette_out_args(res),
+                                   C.c_void_p(s.data_ptr()) if s is not None else None, C.byref(st)))
+    res["avg_width_all"] = float(res["avg_width_all"][0])
+    if sums:
+        res["sums"] = s
+    return res, st.as_dict()
+
+
 def region_pca(ctx: _lib.Context, counts: torch.Tensor, rows=None, center: bool = True, ncomp=None,
                scores: bool = True, gram: bool = False):
     """ks_spectra_pca_dev: principal components (R's prcomp, test.R:734-736,
