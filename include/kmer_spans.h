@@ -1108,6 +1108,127 @@ ks_status ks_spectra_pca(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_
  * hold P / 2 entries.  Returns the pair count, -1 for a bad argument. */
 int32_t ks_pca_round_pairs(int32_t ncol, int32_t round, int32_t *p, int32_t *q);
 
+/* ---------------------------------------------------------------------
+ * Lloyd k-means and group mean spectra of region spectra
+ * (csrc/ks_kmeans.hip).
+ * --------------------------------------------------------------------- */
+
+/* Every other way of grouping regions here goes through the condensed distance
+ * matrix (ks_spectra_dist -> ks_hclust / ks_nj -> ks_hclust_cut ->
+ * ks_silhouette), n(n-1)/2 doubles.  These entries work on the counts: the mean
+ * spectrum of every group of a labelling, and R's kmeans(x, centers, iter.max,
+ * algorithm = "Lloyd") on the row-normalised profiles, in O((m + g) ncol)
+ * memory, with nothing of size m x g or m x m.
+ *
+ * Input: a spectra matrix as ks_region_spectra_dev writes it, n x ncol uint32,
+ * row-major, 1 <= ncol <= KS_DIST_MAX_NCOL, and an optional int64 row selection
+ * as in ks_spectra_pca_dev (any order, repeats allowed; NULL with a count of m
+ * means rows 0 .. m - 1, m > n is an error then).  m >= 1.  Row s below is
+ * position s of the selection.
+ * Profile: p[s][c] = (double)cnt / (double)T, T the row sum in 64-bit integers,
+ * one IEEE division: the profile of ks_spectra_dist.  A selected row with
+ * T = 0 is KS_ERR_ARG, "row s has no counts"; a bad index is KS_ERR_ARG, "row
+ * index s out of range"; each names the first such position, and the index
+ * error is reported before the empty row.
+ *
+ * Definitions, each a separate FP64 operation (no FMA), so that a short host
+ * loop reproduces every output bit for bit:
+ *   Squared distance of row s and centre j: acc = +0.0; for c ascending:
+ *   d = p[s][c] - cen[j][c]; acc = acc + d * d.  One accumulator per (s, j): the
+ *   inner loop of ks_spectra_dist.  Where cen[j] is the profile of a row r the
+ *   value carries the bits of ks_spectra_cross_dist(..., KS_DIST_SQUARED) for
+ *   (s, r).  (No Gram form, no MFMA: see csrc/ks_spectra_dist.hip.)
+ *   Assignment: label[s] = the j with the smallest acc, scanning j ascending
+ *   from +inf with a strict <, so the lowest label wins a tie.  Labels are
+ *   1 .. g, as ks_hclust_cut writes them.
+ *   Group sum of a value v(s) over group j: the members of j in ascending
+ *   position order are cut into chunks of KS_KM_CHUNK consecutive members.
+ *   Chunk partial: P = +0.0, then P = P + v(s) over the chunk's members,
+ *   ascending.  S = +0.0, then S = S + P_q over the chunks, ascending.  (The
+ *   order of ks_silhouette's sums.)
+ *   Centre: cen[j][c] = S_j[c] / (double)n_j with v(s) = p[s][c], n_j the size.
+ *   In k-means a group without members keeps the bits of its previous centre
+ *   (a definition of this library: R stops with "empty cluster"); in the
+ *   group-means entries it gets a row of NaN.
+ *   withinss[j] = the group sum with v(s) = acc(s, j) against the returned
+ *   centres, +0.0 for an empty group.  tot_withinss = the left-to-right sum of
+ *   withinss over j from +0.0.  totss = the same two definitions for the
+ *   single group of all m rows: its chunked centre, then its chunked sum.
+ *   Loop (R's kmeans_Lloyd): the labels start at 0.  For iter = 1 .. iter_max:
+ *   assign; if no label changed, stop with converged = 1; otherwise recompute
+ *   every centre.  iter is the number of assignment passes run.  After the
+ *   iter_max-th pass the centres are still updated, so, as in R, the labels of
+ *   a run that did not converge need not be the nearest centres of the
+ *   returned centres; withinss uses the returned labels and centres always.
+ * Initial centres: exactly one of init (g x ncol doubles, row-major; every
+ * entry finite, otherwise KS_ERR_ARG, "center[j][c] is not finite", the first
+ * such entry in row-major order) and init_rows (g int64 positions into the
+ * selection: the centre is that row's profile, bit for bit; a position outside
+ * 0 .. m - 1 is KS_ERR_ARG, "initial row index j out of range", the first such
+ * j).  Neither or both is KS_ERR_ARG.  Duplicate centres are allowed: the tie
+ * rule decides.  1 <= g <= KS_KM_MAX_GROUPS; g > m is allowed; iter_max >= 1;
+ * flags must be 0.
+ * The result is a function of the input alone, with the same bits on every
+ * run: no atomics on doubles, no reduction that depends on arrival order. */
+#define KS_KM_CHUNK 256
+#define KS_KM_MAX_GROUPS 65536
+typedef struct ks_kmeans_result {
+  int32_t iter;        /* assignment passes run */
+  int32_t converged;   /* 1: the last pass changed no label */
+  double tot_withinss;
+  double totss;
+} ks_kmeans_result;
+typedef struct ks_kmeans_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total;
+  double ms_normalise; /* checks, profiles, initial centres */
+  double ms_assign;    /* summed over the passes (each with its 4-byte read-back queued behind it) */
+  double ms_update;    /* member list and centres, summed over the passes; group means: the one update */
+  double ms_wss;       /* withinss, and totss in k-means */
+  int64_t n_iter;
+  int64_t panel_bytes; /* the m x ncol FP64 profile panel */
+  int64_t work_bytes;  /* the rest of the call's one allocation: chunk partials ((m / 256 + g) x ncol doubles), the
+                          member list and sort buffers (O(m)), the split minima of the assignment (12 m bytes
+                          per split; splits only while there are fewer than 32 workgroups per CU) and O(g) tables.  Allocated and freed by the call. */
+} ks_kmeans_stats;
+
+/* Device-resident: spectra_dev, rows_dev, init_dev, init_rows_dev, cluster_dev
+ * (int32[m]) and centers_dev (double[g * ncol]) are device pointers; size
+ * (int32[g]), withinss (double[g]) and res are host pointers.  centers_dev may
+ * be the same buffer as init_dev.  Indices, row sums and centres are checked
+ * on the device before any output is written: after a rejected call the
+ * outputs are untouched and the context usable.  The only allocation is the
+ * work memory counted in panel_bytes + work_bytes (KS_ERR_NOMEM if it fails),
+ * freed before return.  All other arguments are validated before any device
+ * call.  One 4-byte read-back per pass is the loop's only host round trip.
+ * stats may be NULL.  ctx == NULL is the default context on device 0; the
+ * calls are never spread over a device list and are not forwarded by the fork
+ * broker. */
+ks_status ks_spectra_kmeans_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                                const int64_t *rows_dev, int64_t m, const double *init_dev,
+                                const int64_t *init_rows_dev, int32_t g, int32_t iter_max, int32_t flags,
+                                int32_t *cluster_dev, double *centers_dev, int32_t *size, double *withinss,
+                                ks_kmeans_result *res, ks_kmeans_stats *stats);
+/* Host buffers: validates every argument, every index, every row sum and every
+ * centre before any device call, then uploads, runs the device entry and
+ * copies the results back. */
+ks_status ks_spectra_kmeans(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                            int64_t m, const double *init, const int64_t *init_rows, int32_t g, int32_t iter_max,
+                            int32_t flags, int32_t *cluster, double *centers, int32_t *size, double *withinss,
+                            ks_kmeans_result *res);
+/* The update and the withinss step as an entry of their own (the bridge from
+ * ks_hclust_cut): group is a HOST int32[m] of labels in 1 .. ngroups, checked
+ * on the host before any device call with the text of ks_silhouette ("group[i]
+ * = v is not in 1 .. g"); 1 <= ngroups <= KS_KM_MAX_GROUPS; empty groups are
+ * allowed (a NaN row, size 0, withinss +0.0) and one non-empty group is enough.
+ * centers_dev: double[ngroups * ncol] on the device; size, withinss: host. */
+ks_status ks_spectra_group_means_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                                     const int64_t *rows_dev, int64_t m, const int32_t *group, int32_t ngroups,
+                                     int32_t flags, double *centers_dev, int32_t *size, double *withinss,
+                                     ks_kmeans_stats *stats);
+ks_status ks_spectra_group_means(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                                 int64_t m, const int32_t *group, int32_t ngroups, int32_t flags, double *centers,
+                                 int32_t *size, double *withinss);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

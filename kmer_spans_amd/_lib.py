@@ -135,6 +135,19 @@ class PcaStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class KmeansStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_assign", C.c_double),
+                ("ms_update", C.c_double), ("ms_wss", C.c_double), ("n_iter", C.c_int64),
+                ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class KmeansResult(C.Structure):
+    _fields_ = [("iter", C.c_int32), ("converged", C.c_int32), ("tot_withinss", C.c_double), ("totss", C.c_double)]
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -173,6 +186,7 @@ EXPORTS = [
     "ks_nj", "ks_nj_dev", "ks_nj_edges",
     "ks_silhouette", "ks_silhouette_dev",
     "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
+    "ks_spectra_kmeans", "ks_spectra_kmeans_dev", "ks_spectra_group_means", "ks_spectra_group_means_dev",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
     "ks_scan_chunk_indices", "ks_scan_tile_chunks",
@@ -190,6 +204,8 @@ KS_SIL_CHUNK = 256
 KS_PCA_MAX_NCOL = 1024
 KS_PCA_MAX_SWEEPS = 64
 KS_PCA_NO_CENTER = 1
+KS_KM_CHUNK = 256
+KS_KM_MAX_GROUPS = 65536
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -279,6 +295,10 @@ def load():
         "ks_spectra_pca": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P], I32),
         "ks_spectra_pca_dev": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P, P], I32),
         "ks_pca_round_pairs": ([I32, I32, P, P], I32),
+        "ks_spectra_kmeans": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P], I32),
+        "ks_spectra_kmeans_dev": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P, P], I32),
+        "ks_spectra_group_means": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P], I32),
+        "ks_spectra_group_means_dev": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P, P], I32),
         "ks_seq_index_create": ([P, P], I32),
         "ks_seq_index_destroy": ([P], None),
         "ks_seq_index_info_get": ([P, P], I32),
@@ -463,6 +483,26 @@ def silhouette_group(group, n: int, ngroups=None):
     elif int(ngroups) != ngroups or not 1 <= int(ngroups) <= 0x7fffffff:
         raise KmerSpansError(f"ngroups = {ngroups} is not a positive int32")
     return g, int(ngroups)
+
+
+def kmeans_centers(centers, ncol: int):
+    """(init float64[g, ncol] or None, init_rows int64[g] or None, g) of a
+    centers argument: a 2-d float array is the matrix form, a 1-d integer
+    sequence names positions of the row selection (the library checks both)."""
+    c = np.asarray(centers)
+    if c.ndim == 1 and c.dtype.kind in "iu" and c.size:
+        return None, np.ascontiguousarray(c, dtype=np.int64), int(c.size)
+    if c.ndim == 2 and c.dtype.kind in "fiu" and c.shape[0] and c.shape[1] == ncol:
+        return np.ascontiguousarray(c, dtype=np.float64), None, int(c.shape[0])
+    raise KmerSpansError(f"centers must be a [g, {ncol}] matrix of initial centres or a 1-d sequence of integer "
+                         "row positions")
+
+
+def kmeans_result(res: KmeansResult) -> dict:
+    """The scalar outputs of ks_spectra_kmeans as the dict entries of R's kmeans object."""
+    return {"tot_withinss": float(res.tot_withinss), "totss": float(res.totss),
+            "betweenss": float(res.totss) - float(res.tot_withinss), "iter": int(res.iter),
+            "converged": bool(res.converged)}
 
 
 def silhouette_outputs(n: int, ngroups: int) -> dict:

@@ -320,6 +320,79 @@ def region_pca(counts, rows=None, center: bool = True, ncomp=None, scores: bool 
     return {"sdev": sdev, "rotation": rot, "center": cen, "x": x}
 
 
+def _counts_arg(counts):
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "iu":
+        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
+    if c.dtype != np.uint32:
+        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+            raise KmerSpansError("counts must be in the uint32 range")
+        c = c.astype(np.uint32)
+    return np.ascontiguousarray(c)
+
+
+def region_kmeans(counts, centers, rows=None, iter_max: int = 10, device: int = 0) -> dict:
+    """R's kmeans(x, centers, iter.max, algorithm="Lloyd") on row-normalised
+    spectra, from the counts region_spectra returns, computed on the device
+    without any distance matrix: memory is O((m + g) ncol).
+
+    counts: [n, ncol] non-negative integers (uint32 range), 1 <= ncol <= 4096.
+    rows: optional integer row indices (any order, repeats allowed); None = all
+    rows.  A row's profile is counts / row sum; a selected row without counts
+    is an error naming its position.  centers: a [g, ncol] float matrix of
+    initial centres (every entry finite), or a 1-d sequence of g integer
+    positions into the selection whose profiles are the initial centres.  No
+    random start is offered: the caller draws the positions.  Duplicate centres
+    are allowed; the lowest label wins every tie.  1 <= g <= 65536.  Returns
+    {'cluster': int32[m] labels 1 .. g, 'centers': float64[g, ncol], 'size':
+    int32[g], 'withinss': float64[g], 'tot_withinss', 'totss', 'betweenss'
+    (totss - tot_withinss): float, 'iter': assignment passes run, 'converged':
+    bool}.  A group that loses all its members keeps its centre (R stops
+    there).  As in R, after iter_max passes without convergence the centres
+    are one update ahead of the labels.  Every sum is a fixed order of FP64
+    operations (include/kmer_spans.h): the same input gives the same bits on
+    every run."""
+    c = _counts_arg(counts)
+    n, ncol = (int(v) for v in c.shape)
+    r = _rows_arg(rows, "rows")
+    m = n if r is None else int(r.size)
+    init, init_rows, g = _lib.kmeans_centers(centers, ncol)
+    cluster = np.zeros(max(m, 0), dtype=np.int32)
+    cen = np.zeros((g, ncol), dtype=np.float64)
+    size, wss = np.zeros(g, dtype=np.int32), np.zeros(g, dtype=np.float64)
+    res = _lib.KmeansResult()
+    check(load().ks_spectra_kmeans(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None, m,
+                                   init.ctypes.data if init is not None else None,
+                                   init_rows.ctypes.data if init_rows is not None else None, g, int(iter_max), 0,
+                                   cluster.ctypes.data, cen.ctypes.data, size.ctypes.data, wss.ctypes.data,
+                                   C.byref(res)))
+    return dict({"cluster": cluster, "centers": cen, "size": size, "withinss": wss}, **_lib.kmeans_result(res))
+
+
+def region_group_means(counts, group, ngroups=None, rows=None, device: int = 0) -> dict:
+    """The mean spectrum of every group of a labelling of row-normalised
+    spectra (for instance the groups of cut_tree), with the groups' sizes and
+    within sums of squares: the update and withinss steps of region_kmeans as
+    a call of their own, on the device.
+
+    counts, rows: as for region_kmeans.  group: one integer label in 1 ..
+    ngroups per selected row; ngroups defaults to the largest label.  Returns
+    {'centers': float64[g, ncol] (a row of NaN for a group without members),
+    'size': int32[g], 'withinss': float64[g] (0 for an empty group)}.  The
+    centres can start region_kmeans when no group is empty."""
+    c = _counts_arg(counts)
+    n, ncol = (int(v) for v in c.shape)
+    r = _rows_arg(rows, "rows")
+    m = n if r is None else int(r.size)
+    g, ng = _lib.silhouette_group(group, m, ngroups)
+    ngb = min(ng, _lib.KS_KM_MAX_GROUPS)  # a larger ngroups is the library's error; the buffers only need a size
+    cen = np.zeros((ngb, ncol), dtype=np.float64)
+    size, wss = np.zeros(ngb, dtype=np.int32), np.zeros(ngb, dtype=np.float64)
+    check(load().ks_spectra_group_means(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None,
+                                        m, g.ctypes.data, ng, 0, cen.ctypes.data, size.ctypes.data, wss.ctypes.data))
+    return {"centers": cen, "size": size, "withinss": wss}
+
+
 def region_hclust(dist, method: str = "complete", device: int = 0) -> dict:
     """R's hclust() of a condensed dissimilarity vector (test.R:776), run on
     the device.

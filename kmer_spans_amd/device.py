@@ -686,3 +686,93 @@ def region_pca(ctx: _lib.Context, counts: torch.Tensor, rows=None, center: bool 
                                     ptr(res["sdev"]), ptr(res["rotation"]), ptr(res["x"]), ptr(res.get("G")),
                                     C.byref(st)))
     return res, st.as_dict()
+
+
+def _counts_dev(counts):
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
+            or counts.dim() != 2 or not counts.is_contiguous()):
+        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
+    return counts.device, int(counts.shape[0]), int(counts.shape[1])
+
+
+def region_kmeans(ctx: _lib.Context, counts: torch.Tensor, centers, rows=None, iter_max: int = 10):
+    """ks_spectra_kmeans_dev: R's kmeans(x, centers, iter.max, algorithm="Lloyd")
+    on the row-normalised spectra of region_spectra, on the device and without
+    any distance matrix (memory O((m + g) ncol)).
+
+    counts: the int32 CUDA tensor [n, ncol] region_spectra returns (uint32
+    bits), used in place; 1 <= ncol <= 4096.  rows: an optional selection of
+    row indices, an int64 CUDA tensor (used in place) or numpy (uploaded); any
+    order, repeats allowed; None = all rows.  centers: a float64 [g, ncol]
+    matrix of finite initial centres (a CUDA tensor, read only, or numpy), or a
+    1-d integer sequence or tensor of g positions into the selection whose
+    profiles start the run.  A selected row without counts, a bad index or a
+    non-finite centre is an error naming its position, and nothing is written
+    then.  Returns (res, stats): res is a dict of 'cluster' (int32 CUDA tensor
+    [m], labels 1 .. g), 'centers' (float64 CUDA tensor [g, ncol]), 'size'
+    (int32 numpy [g]), 'withinss' (float64 numpy [g]) and the scalars
+    'tot_withinss', 'totss', 'betweenss', 'iter', 'converged'; stats the dict
+    of ks_kmeans_stats.  include/kmer_spans.h has the order of every
+    operation; one 4-byte read-back per pass is the only host round trip."""
+    dev, n, ncol = _counts_dev(counts)
+    r = _rows_dev(rows, "rows", dev) if rows is not None else None
+    m = n if r is None else int(r.numel())
+    init = init_rows = None
+    if isinstance(centers, torch.Tensor) and centers.dim() == 2:
+        if centers.dtype != torch.float64 or centers.shape[1] != ncol or not centers.shape[0]:
+            raise _lib.KmerSpansError(f"a centers tensor must be float64 [g, {ncol}]")
+        init = centers.to(dev).contiguous()
+        g = int(init.shape[0])
+    elif isinstance(centers, torch.Tensor):
+        init_rows = _rows_dev(centers, "centers", dev)
+        g = int(init_rows.numel())
+        if not g:
+            raise _lib.KmerSpansError("centers names no row")
+    else:
+        hi, hr, g = _lib.kmeans_centers(centers, ncol)
+        if hi is not None:
+            init = torch.from_numpy(hi).to(dev)
+        else:
+            init_rows = torch.from_numpy(hr).to(dev)
+    cluster = torch.empty(m, dtype=torch.int32, device=dev)
+    cen = torch.empty((g, ncol), dtype=torch.float64, device=dev)
+    size, wss = np.zeros(g, dtype=np.int32), np.zeros(g, dtype=np.float64)
+    out, st = _lib.KmeansResult(), _lib.KmeansStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    _order(ctx)
+    check(load().ks_spectra_kmeans_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n, ncol,
+                                       ptr(r), m, ptr(init), ptr(init_rows), g, int(iter_max), 0, ptr(cluster),
+                                       ptr(cen), size.ctypes.data, wss.ctypes.data, C.byref(out), C.byref(st)))
+    res = dict({"cluster": cluster, "centers": cen, "size": size, "withinss": wss}, **_lib.kmeans_result(out))
+    return res, st.as_dict()
+
+
+def region_group_means(ctx: _lib.Context, counts: torch.Tensor, group, ngroups=None, rows=None):
+    """ks_spectra_group_means_dev: the mean spectrum, size and within sum of
+    squares of every group of a labelling (for instance cut_tree's) of the
+    row-normalised spectra, on the device: the bridge from a tree cut to
+    region_kmeans.
+
+    counts, rows: as for region_kmeans.  group: one integer label in 1 ..
+    ngroups per selected row, a numpy array or a tensor (a CUDA tensor is
+    downloaded, 4 m bytes); ngroups defaults to the largest label; groups
+    without members are allowed.  Returns (res, stats): res is a dict of
+    'centers' (float64 CUDA tensor [g, ncol], a row of NaN for an empty group),
+    'size' (int32 numpy [g]) and 'withinss' (float64 numpy [g]); stats the dict
+    of ks_kmeans_stats."""
+    dev, n, ncol = _counts_dev(counts)
+    r = _rows_dev(rows, "rows", dev) if rows is not None else None
+    m = n if r is None else int(r.numel())
+    if isinstance(group, torch.Tensor):
+        group = group.detach().cpu().numpy()
+    g, ng = _lib.silhouette_group(group, m, ngroups)
+    ngb = min(ng, _lib.KS_KM_MAX_GROUPS)  # a larger ngroups is the library's error; the buffers only need a size
+    cen = torch.empty((ngb, ncol), dtype=torch.float64, device=dev)
+    size, wss = np.zeros(ngb, dtype=np.int32), np.zeros(ngb, dtype=np.float64)
+    st = _lib.KmeansStats()
+    _order(ctx)
+    check(load().ks_spectra_group_means_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n,
+                                            ncol, C.c_void_p(r.data_ptr()) if r is not None and r.numel() else None,
+                                            m, g.ctypes.data, ng, 0, C.c_void_p(cen.data_ptr()), size.ctypes.data,
+                                            wss.ctypes.data, C.byref(st)))
+    return {"centers": cen, "size": size, "withinss": wss}, st.as_dict()
