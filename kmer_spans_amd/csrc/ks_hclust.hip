@@ -182,6 +182,7 @@ __global__ void __launch_bounds__(kHcThreads) k_hclust_pair(double *d, int n, in
   // their entries exist) is issued before its first store, so the scattered
   // reads overlap instead of queueing behind stores they might alias
   const int stride = gridDim.x * kHcThreads;
+  // no test reaches a second pass of this loop: it needs n > kHcChunk * kHcPairBlocks * kHcThreads = 32,768 (4.3 GB)
   for (int k0 = blockIdx.x * kHcThreads + tid; k0 < n; k0 += kHcChunk * stride) {
     double x[kHcChunk], y[kHcChunk];
     int t[kHcChunk];

@@ -244,6 +244,7 @@ __global__ void __launch_bounds__(kNjThreads) k_nj_join(double *d, int m, int r,
   // kNjChunk k per thread at a time: every load of a chunk is issued before
   // its first store, so the scattered reads overlap
   const int stride = gridDim.x * kNjThreads;
+  // no test reaches a second pass of this loop: it needs m > kNjChunk * kNjJoinBlocks * kNjThreads = 32,768 (4.3 GB)
   for (int k0 = blockIdx.x * kNjThreads + tid; k0 < m; k0 += kNjChunk * stride) {
     double x[kNjChunk], y[kNjChunk], sk_[kNjChunk];
     bool lv[kNjChunk];

@@ -295,6 +295,166 @@ def test_host_entry(ctx, tie_free, method):
     assert host["method"] == method
 
 
+# ------------------------------------- the finiteness pass past its first stride
+
+def check_stride(max_bytes=1 << 30):
+    """(E, n): the entries a full grid of check_all_finite (8 * num_cus blocks
+    of 256 threads, 16 bytes a thread) reads in one stride, and the smallest n
+    whose condensed vector holds an odd count of more than 2 E + 3 entries, so
+    that some threads take a third item and thread 0 the odd tail."""
+    import torch
+    num_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    E = 2 * 256 * 8 * num_cus
+    n = int(np.sqrt(4.0 * E)) - 2
+    while n * (n - 1) // 2 <= 2 * E + 3 or not (n * (n - 1) // 2) & 1:
+        n += 1
+    if 8 * (n * (n - 1) // 2) > max_bytes:
+        pytest.skip(f"{num_cus} CUs: a vector of more than two strides of the check would pass 1 GB")
+    return E, n
+
+
+@pytest.fixture(scope="module")
+def long_vector():
+    """(E, n, finite values on the device); the tests work on clones."""
+    import torch
+    E, n = check_stride()
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    return E, n, torch.rand(n * (n - 1) // 2, dtype=torch.float64, device="cuda", generator=gen)
+
+
+def assert_names(call, d, at):
+    """call(d, keep) is refused naming offset `at`, keep_input both ways, and no bit of d changes."""
+    import torch
+    import kmer_spans_amd as K
+    before = d.clone()
+    for keep in (False, True):
+        with pytest.raises(K.KmerSpansError, match=f"^dissimilarity at offset {at} is not finite$"):
+            call(d, keep)
+        assert torch.equal(d.view(torch.int64), before.view(torch.int64)), (at, keep, "the input changed")
+
+
+PLANTS = {"E-1": lambda E, total: E - 1, "E": lambda E, total: E, "E+1": lambda E, total: E + 1,
+          "2E+1": lambda E, total: 2 * E + 1, "last": lambda E, total: total - 1}
+
+
+@pytest.mark.parametrize("where", list(PLANTS))
+@pytest.mark.parametrize("bad", [np.inf, np.nan])
+def test_planted_past_the_first_stride(ctx, long_vector, where, bad):
+    """One bad entry where only a later grid-stride item of k_hclust_check
+    reads it: the last entry of the first stride, the first two of the second,
+    one of the third, and the odd tail that thread 0 reads after its loop
+    (n = 2,050 at 256 CUs: 2,100,225 entries, 0.1 s a case)."""
+    from kmer_spans_amd import device as D
+    E, n, src = long_vector
+    total = src.numel()
+    assert total > 2 * E + 3 and total & 1 and src.data_ptr() % 16 == 0
+    at = PLANTS[where](E, total)
+    d = src.clone()
+    assert d.data_ptr() % 16 == 0
+    d[at] = float(bad)
+    assert_names(lambda x, keep: D.region_hclust(ctx, x, keep_input=keep), d, at)
+
+
+def test_two_planted_the_lower_is_named(ctx, long_vector):
+    """Two bad entries: the lower one at a later item of a higher thread than
+    the higher one (the threads settle it by atomicMin), then both in one
+    thread (its first hit stays)."""
+    from kmer_spans_amd import device as D
+    E, n, src = long_vector
+    threads = E // 2  # a thread reads two entries per item
+    for lo, hi in ((E + 2 * (threads - 1), 2 * E + 3), (E + 6, 2 * E + 6), (E - 3, E + 1)):
+        assert lo < hi < src.numel()
+        d = src.clone()
+        d[lo], d[hi] = float("nan"), float("-inf")
+        assert_names(lambda x, keep: D.region_hclust(ctx, x, keep_input=keep), d, lo)
+
+
+@pytest.mark.parametrize("where", ["E/2-1", "E/2", "E+1", "last"])
+def test_planted_past_the_first_stride_unaligned(ctx, long_vector, where):
+    """The same on a view that starts 8 bytes into an allocation: k_hclust_check1
+    reads one entry per item, so its stride is E / 2 entries."""
+    import torch
+    from kmer_spans_amd import device as D
+    E, n, src = long_vector
+    buf = torch.empty(src.numel() + 1, dtype=torch.float64, device="cuda")
+    view = buf[1:]
+    view.copy_(src)
+    assert view.data_ptr() % 16 == 8
+    at = {"E/2-1": E // 2 - 1, "E/2": E // 2, "E+1": E + 1, "last": src.numel() - 1}[where]
+    view[at] = float("inf")
+    if at + E // 2 < src.numel():
+        view[at + E // 2] = float("nan")  # the same thread's next item
+    assert_names(lambda x, keep: D.region_hclust(ctx, x, keep_input=keep), view, at)
+
+
+def test_nj_and_silhouette_past_the_first_stride(ctx, long_vector):
+    """region_nj and region_silhouette run the same pass, each with a result word of its own."""
+    from kmer_spans_amd import device as D
+    E, n, src = long_vector
+    group = (np.arange(n) % 2 + 1).astype(np.int32)
+    d = src.clone()
+    d[E + 1] = float("nan")
+    assert_names(lambda x, keep: D.region_nj(ctx, x, keep_input=keep), d, E + 1)
+    d = src.clone()
+    d[2 * E + 1] = float("inf")
+    assert_names(lambda x, keep: D.region_silhouette(ctx, x, group), d, 2 * E + 1)
+    d[E] = float("nan")
+    assert_names(lambda x, keep: D.region_nj(ctx, x, keep_input=keep), d, E)
+    good = src[:10].clone()  # the words are clear again: n = 5 goes through
+    D.region_hclust(ctx, good)
+    D.region_nj(ctx, good)
+
+
+# ------------------------------------ exact, where the blocks of a step multiply
+
+@pytest.mark.parametrize("method", METHODS)
+@pytest.mark.parametrize("n", [4096, 4097])
+def test_two_pair_blocks(ctx, tie_free, n, method):
+    """The last grid of one k_hclust_pair block and the first of two: from
+    4,097 on every block repeats the arg-min, the blocks share the k of the row
+    update (k0 + u * 2048) and append to one list.  ref_tree takes 1.3 s at
+    this size on a slow host (complete and average; single 0.8 s); a case,
+    reference included, 0.4 to 0.7 s on the MI355X machine."""
+    check_device(ctx, tie_free(ctx, n), method, f"n={n} {method}")
+
+
+@pytest.mark.parametrize("method", ["complete", "average"])
+def test_three_pair_blocks(ctx, tie_free, method):
+    """n = 8,193: three blocks, k = k0 + u * 3072.  ref_tree is most of the
+    test's time: about 5 s on a slow host, and the whole case 1.7 s on the
+    MI355X machine."""
+    check_device(ctx, tie_free(ctx, 8193), method, f"n=8193 {method}")
+
+
+TIE_RICH_V = 128
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_two_pair_blocks_tie_rich(ctx, method):
+    """n = 4,097, integers from {0 .. V-1}, V = 128, as star_ties of
+    tests/test_hclust.py lays them out: up to 63 rows are listed in one step,
+    by both blocks of k_hclust_pair, and rescanned in four rounds of the 16
+    blocks of k_hclust_rescan.  The order of the list is whatever the atomic
+    counter gives; the tree and the count must not depend on it.
+
+    ref_tree alone, measured on the host: complete 1.0 s and 27,023 rescans,
+    single 1.8 s and 135,068, average 1.0 s and 27,133, against 4 n = 16,388
+    (a case on the MI355X machine, reference included: 0.6, 1.0 and 0.6 s).
+    Every V from 1 up finishes in under 2 s, so the time does not choose V;
+    V = 128 is the smallest power of two at which a step lists several times
+    the 16 rows that k_hclust_rescan takes side by side (V = 16 is the
+    smallest that reaches 4 n for every method, with at most 7 rows a step).
+    Uniform integers never reach 4 n for single linkage (star_ties has the
+    figures), which is why the input is laid out."""
+    from tests.test_hclust import star_ties
+    n = 4097
+    d = star_ties(np.random.default_rng(n), n, TIE_RICH_V)
+    assert d.min() == 0 and d.max() == TIE_RICH_V - 1 and (d == np.floor(d)).all()
+    _, st, want = check_device(ctx, dist_dev(d), method, f"tie rich n={n} {method}")
+    print(f"n = {n} {method} V = {TIE_RICH_V}: {want['n_rescans']} rescans in {n - 1} steps")
+    assert want["n_rescans"] >= 4 * n
+
+
 # -------------------------------------------------------- scale: invariants
 
 @pytest.fixture(scope="module")
@@ -307,8 +467,11 @@ def big(ctx):
 
 @pytest.mark.parametrize("method", METHODS)
 def test_scale_invariants(ctx, big, method):
-    """n = 8,192 (268 MB): the host reference is too slow here, so only what
-    must hold of any tree of this contract."""
+    """n = 8,192 (268 MB): what must hold of any tree of this contract, for all
+    three methods.  A tree built from a stale nearest neighbour can satisfy all
+    of it; the host reference is not too slow at this size (about 5 s a
+    method), and test_two_pair_blocks and test_three_pair_blocks compare
+    against it exactly at n = 4,096, 4,097 and 8,193."""
     import kmer_spans_amd as K
     from kmer_spans_amd import device as D
     n, d = big

@@ -1,8 +1,9 @@
 """Neighbour joining on the device (ks_nj_dev / ks_nj) against the host
 reference of tests/test_nj.py: join, root and the bits of length and
-root_length identical, with and without compaction; beyond the reference's
-reach, additive trees that must come back exactly.  Runs on an MI355X
-(pytest -m gpu)."""
+root_length identical, with and without compaction; beyond the numpy
+reference's reach, additive trees that must come back exactly, and at
+n = 4,100 the torch transcription of tests/njref.py on the device.  Runs on an
+MI355X (pytest -m gpu)."""
 import numpy as np
 import pytest
 
@@ -280,12 +281,17 @@ def test_host_entry(ctx, tie_free):
 
 # ------------------------------------------- beyond the numpy loop's reach
 
-@pytest.mark.parametrize("n", [1025, 2049])
+@pytest.mark.parametrize("n", [1025, 2049, 2051, 8200])
 def test_additive_trees_come_back_exactly(ctx, n):
     """Rows longer than one block pass.  Branch lengths are multiples of 1/64
     up to 4 and a path has at most n of them: every sum the algorithm forms
     (row sums: n paths) stays below 4 n^2 < 2^53 / 64, so all of it is exact and
-    the tree's path lengths are the input."""
+    the tree's path lengths are the input.  n = 2,051: 1,025 block minima, the
+    first second pass of k_nj_join's reduction over them.  n = 8,200: 4,100 row
+    pairs for the 2,048 blocks of k_nj_min, so every block walks two or three
+    and merges their minima; three k_nj_join blocks; compactions from 8,200
+    and from 4,100 rows (the host builds the 538 MB square once, 3.6 s)."""
+    assert 4 * n * n < 2 ** 53 // 64
     from kmer_spans_amd import device as D
     rng = np.random.default_rng(n)
     d = random_additive(rng, n)
@@ -297,3 +303,60 @@ def test_additive_trees_come_back_exactly(ctx, n):
     assert st["n_compactions"] == predicted_compactions(n)
     flat, _ = D.region_nj(ctx, dev, compact=False)
     assert_same_nj(flat, tree, "without compaction")
+
+
+# ------------------------------- exact, where k_nj_min's grid is capped
+
+BIG_N = 4100
+# The steps the torch reference runs: all n - 3 = 4,097.  Measured on the MI355X, ref_nj_torch on
+# "cuda" takes 2.83 s on the tie-free input and 1.99 s on the tie-heavy one, the two tests 3.0 s
+# and 2.2 s in all (pytest --durations=0).  Were a test to pass 10 s, this would be
+# the largest multiple of 256 that stays within it, never fewer than 256 -- and a prefix is never
+# shortened to make a failure go away.
+BIG_STEPS = BIG_N - 3
+
+
+def check_big(ctx, dist, key):
+    """device.region_nj at n = 4,100 against ref_nj_torch (tests/njref.py) run
+    on "cuda" on the downloaded bits: join equal and length bit-equal over the
+    reference's steps, root and root_length when it runs to the end; then
+    compact=False against compact=True over all steps."""
+    import time
+    from kmer_spans_amd import device as D
+    from tests.njref import ref_nj_torch
+    n = BIG_N
+    host = dist.cpu().numpy()
+    assert host.size == n * (n - 1) // 2
+    t0 = time.perf_counter()
+    want = ref_nj_torch(host, n, compact=True, steps=BIG_STEPS, device="cuda")
+    print(f"{key}: ref_nj_torch on cuda, {want['steps']} of {n - 3} steps in {time.perf_counter() - t0:.2f} s")
+    k = want["steps"]
+    assert k == BIG_STEPS >= 256 and (k == n - 3 or k % 256 == 0)
+    tree, st = D.region_nj(ctx, dist)
+    assert np.array_equal(bits(dist.cpu().numpy()), bits(host)), (key, "keep_input=True changed the input")
+    differ = np.flatnonzero((tree["join"][:k] != want["join"]).any(axis=1))
+    assert differ.size == 0, (key, "join from step", int(differ[0]), tree["join"][differ[0]], want["join"][differ[0]])
+    assert np.array_equal(bits(tree["length"][:k]), bits(want["length"])), (key, "length")
+    if k == n - 3:
+        assert_same_nj(tree, want, key)
+        assert want["n_compactions"] == predicted_compactions(n)
+    assert st["n"] == n and st["n_compactions"] == predicted_compactions(n), (key, st)
+    flat, st_flat = D.region_nj(ctx, dist, compact=False)
+    assert_same_nj(flat, tree, f"{key} without compaction")
+    assert st_flat["n_compactions"] == 0 and st_flat["work_bytes"] == 8 * host.size
+
+
+def test_capped_grid_tie_free(ctx, tie_free):
+    """n = 4,100: 2,050 row pairs for 2,048 k_nj_min blocks, so blocks 0 and 1
+    walk two pairs and merge their minima; two k_nj_join blocks share the k of
+    the update; 2,048 block minima take two passes of the join's reduction;
+    the first compaction is from 4,100 rows, five to a thread in k_nj_rank."""
+    check_big(ctx, tie_free(ctx, BIG_N), f"tie free {BIG_N}")
+
+
+def test_capped_grid_tie_heavy(ctx):
+    """The same with distances from {1, 2, 3}: across the pairs a block walks
+    and across the blocks, equal q must fall to the lower (i, j)."""
+    rng = np.random.default_rng(BIG_N)
+    d = rng.integers(1, 4, size=BIG_N * (BIG_N - 1) // 2).astype(np.float64)
+    check_big(ctx, dist_dev(d), f"ties {BIG_N}")

@@ -150,6 +150,40 @@ def line_dist(x) -> np.ndarray:
     return np.abs(x[i] - x[j])
 
 
+def star_ties(rng, n: int, V: int) -> np.ndarray:
+    """Tie-rich input that keeps the rescan lists long: integers from
+    {0 .. V-1}, condensed.  Uniform integers do not do that: the cluster of
+    row 0 swallows its neighbours in index order and a step lists about one
+    row (single linkage at n = 4,097: n + 5 rescans for V = 8, 2.7 n without
+    any tie).  Here every pair draws from {V/2 .. V-1}, except within stars:
+    with m = V / 2 and G = n // (m + 1), star g holds the rows g + G t,
+    t = 0 .. m, the last of them its hub, and D(row t, hub) = m - 1 - t.  All
+    m rows of a star have the hub as their nearest neighbour; when the closest
+    of them merges with it the other m - 1 are listed at once, for single
+    linkage again at every later merge within the star, and every star holds
+    the same values.  The members of a star lie G rows apart, so the blocks of
+    k_hclust_pair list rows in the same step."""
+    m = V // 2
+    G = n // (m + 1)
+    assert m >= 2 and G >= 1
+    D = rng.integers(m, V, size=(n, n)).astype(np.float64)
+    for t in range(m):
+        g = np.arange(G)
+        D[g + G * t, g + G * m] = float(m - 1 - t)
+    i, j = np.triu_indices(n, 1)
+    return D[i, j].copy()
+
+
+def test_star_ties_keep_the_lists_long():
+    """The property the device test asserts at n = 4,097, at a size that costs
+    nothing here: at least 4 n rescans for every method."""
+    n, V = 521, 32
+    d = star_ties(np.random.default_rng(n), n, V)
+    assert d.min() == 0 and d.max() == V - 1 and (d == np.floor(d)).all()
+    for method in METHODS:
+        assert ref_tree(d, n, method)["n_rescans"] >= 4 * n, method
+
+
 # -------------------------------------------------------------- known answers
 
 LINE5 = [0.0, 1.0, 3.0, 7.0, 15.0]

@@ -213,9 +213,56 @@ def test_additive_trees_come_back_exactly(n):
         assert_additive_exact(ref_nj(d, n, compact), d, n, i, j, f"n={n}")
 
 
+# ------------------------------------- the torch reference (tests/njref.py)
+
+def torch_ref_cases():
+    """(name, n, d): the inputs that tie ref_nj_torch to ref_nj."""
+    def size(n):
+        return n * (n - 1) // 2
+    out = [(f"uniform {n}", n, np.random.default_rng(n).random(size(n))) for n in (5, 65, 257)]
+    out.append(("ties 130", 130, np.random.default_rng(130).integers(1, 4, size=size(130)).astype(np.float64)))
+    out.append(("signed zeros 200", 200, np.random.default_rng(200).choice(np.array([-0.0, 0.0, 1.0, 2.0]), size=size(200))))
+    out.append(("all equal 60", 60, np.full(size(60), 0.75)))
+    return out
+
+
+@pytest.mark.parametrize("case", torch_ref_cases(), ids=lambda c: c[0])
+def test_torch_reference_equals_the_numpy_reference(case):
+    """ref_nj_torch on the CPU against ref_nj, every bit, masked and compacting."""
+    pytest.importorskip("torch")
+    from tests.njref import ref_nj_torch
+    name, n, d = case
+    if name.startswith("signed"):
+        assert np.signbit(d).any() and (~np.signbit(d) & (d == 0)).any()
+    want = ref_nj(d, n)
+    for compact in (False, True):
+        got = ref_nj_torch(d, n, compact=compact, device="cpu")
+        assert_same_nj(got, want, f"{name} compact={compact}")
+        assert got["n_compactions"] == (predicted_compactions(n) if compact else 0) and got["steps"] == n - 3
+
+
+@pytest.mark.parametrize("compact", [False, True])
+def test_torch_reference_prefix(compact):
+    """steps=k returns the first k rows of the full result and no root."""
+    pytest.importorskip("torch")
+    from tests.njref import ref_nj_torch
+    n = 65
+    d = np.random.default_rng(65).random(n * (n - 1) // 2)
+    full = ref_nj_torch(d, n, compact=compact)
+    for k in (0, 1, 31, 40, n - 3):  # 33 live rows after step 31: across the first compaction
+        head = ref_nj_torch(d, n, compact=compact, steps=k)
+        assert head["steps"] == k and head["join"].shape == (k, 2) and head["length"].shape == (k, 2)
+        assert np.array_equal(head["join"], full["join"][:k])
+        assert np.array_equal(bits(head["length"]), bits(full["length"][:k]))
+        if k < n - 3:
+            assert head["root"] is None and head["root_length"] is None
+        else:
+            assert_same_nj(head, full, "the whole loop")
+
+
 # ------------------------------------------------------------- known answers
 
-FIVE = [5, 9, 9, 8, 10, 10, 9, 8, 7, 3]  # the textbook five taxa a .. e
+FIVE =[5, 9, 9, 8, 10, 10, 9, 8, 7, 3]  # the textbook five taxa a .. e
 FIVE_TREE = {"join": [[-1, -2], [1, -3]], "length": [[2.0, 3.0], [3.0, 4.0]], "root": [2, -4, -5],
              "root_length": [2.0, 2.0, 1.0]}
 
