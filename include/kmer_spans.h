@@ -1229,6 +1229,88 @@ ks_status ks_spectra_group_means(ks_ctx *ctx, const uint32_t *spectra, int64_t n
                                  int64_t m, const int32_t *group, int32_t ngroups, int32_t flags, double *centers,
                                  int32_t *size, double *withinss);
 
+/* ---------------------------------------------------------------------
+ * k nearest regions by spectrum, without the distance matrix
+ * (csrc/ks_knn.hip).
+ * --------------------------------------------------------------------- */
+
+/* For every selected row, the k rows of a candidate selection nearest to it
+ * in ks_spectra_dist's metric, in O((na + nb) ncol + na k) memory: nothing of
+ * size na x nb is written or sorted.
+ *
+ * Input: a spectra matrix as ks_region_spectra_dev writes it, n x ncol uint32,
+ * row-major, 1 <= ncol <= KS_DIST_MAX_NCOL.
+ * Queries: an optional int64 selection `rows` of na >= 1 row indices (any
+ * order, repeats allowed; NULL with a count of na means rows 0 .. na - 1,
+ * na > n is an error then).  Query s below is position s of that selection.
+ * Candidates: an optional int64 selection `rows_b` of nb >= 1 row indices.
+ *   Self form (rows_b NULL; nb is ignored): the candidates are the query
+ *   selection itself, and position s is left out of the list of query s.  The
+ *   exclusion is by POSITION, not by row index: a row named twice finds its
+ *   other copy at a distance of exactly 0.  There are na - 1 candidates.
+ *   Cross form: every one of the nb candidates counts.
+ * 1 <= k <= KS_KNN_MAX_K, and k may not exceed the number of candidates
+ * (na - 1 or nb).  flags: 0 or KS_DIST_SQUARED.
+ *
+ * Errors of the selections are KS_ERR_ARG, each names the first offending
+ * position, and they take precedence in this order:
+ *   1. "row index s out of range" (the queries, then the candidates: "row
+ *      index s of the second selection out of range");
+ *   2. "row s has no counts" (the queries, then "row s of the second selection
+ *      has no counts"): an empty row has no profile and is refused, as in
+ *      ks_spectra_kmeans;
+ *   3. "k exceeds the number of candidate rows".
+ * Any of them is raised before an output byte is written.
+ *
+ * Distance: the profile is p[c] = (double)cnt / (double)T, T the row sum in
+ * 64-bit integers.  For query a and candidate b: acc = +0.0; for c ascending:
+ * d = p_a[c] - p_b[c]; acc = acc + d * d, each a separate FP64 operation (no
+ * FMA), one accumulator per pair: acc has the bits of ks_spectra_cross_dist(
+ * ..., KS_DIST_SQUARED) for the pair.  (No Gram form, no MFMA: see
+ * csrc/ks_spectra_dist.hip.)
+ * Selection: the k candidates with the smallest (acc, position) pairs in
+ * lexicographic order, ascending; position is the candidate's position in its
+ * selection.  The comparison is made on acc, the squared value, before any
+ * root is taken (two different acc can share a square root).  acc is never
+ * -0.0 or NaN, so this is a total order and the result is a function of the
+ * input alone: no tile shape, grid or split of the candidates shows in it, and
+ * a host sort of (acc, position) predicts every output.
+ * Outputs, row-major, column 0 the nearest:
+ *   index: int64 [na][k], 0-based positions into the candidate selection (not
+ *          row indices);
+ *   dist:  double [na][k], acc with KS_DIST_SQUARED, otherwise sqrt(acc). */
+#define KS_KNN_MAX_K 64
+typedef struct ks_knn_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total;
+  double ms_normalise;     /* checks and profiles, with the one read-back */
+  double ms_select;        /* k_knn_select */
+  double ms_merge;         /* k_knn_merge; 0 with one split */
+  int64_t n_splits;        /* parts the candidate tiles were cut into (grid y of the selection) */
+  int64_t tiles_per_split; /* candidate tiles of 64 per split; the last split may hold fewer */
+  int64_t panel_bytes;     /* the FP64 profile panel: na x ncol, and nb x ncol more in the cross form */
+  int64_t work_bytes;      /* the rest of the call's one allocation: with more than one split the splits'
+                              lists, 12 bytes x na x k x n_splits.  Allocated and freed by the call. */
+} ks_knn_stats;
+
+/* Device-resident: spectra_dev, rows_dev, rows_b_dev, index_dev (int64
+ * [na * k]) and dist_dev (double [na * k]) are device pointers.  Indices and
+ * row sums are checked on the device and one read-back ends a rejected call
+ * before any output is written: the outputs are untouched then and the
+ * context usable.  The only allocation is the work memory counted in
+ * panel_bytes + work_bytes (KS_ERR_NOMEM if it fails), freed before return.
+ * All other arguments are validated before any device call.  stats may be
+ * NULL.  ctx == NULL is the default context on device 0; the call is never
+ * spread over a device list and is not forwarded by the fork broker. */
+ks_status ks_spectra_knn_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                             const int64_t *rows_dev, int64_t na, const int64_t *rows_b_dev, int64_t nb, int32_t k,
+                             int32_t flags, int64_t *index_dev, double *dist_dev, ks_knn_stats *stats);
+/* Host buffers: validates every argument, every index and every row sum before
+ * any device call, then uploads, runs the device entry and copies the results
+ * back. */
+ks_status ks_spectra_knn(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                         int64_t na, const int64_t *rows_b, int64_t nb, int32_t k, int32_t flags, int64_t *index,
+                         double *dist);
+
 /* Scan algorithm selection (testing/benchmarking): -1 auto, 0 lane-per-run,
  * 1 chunked carry scan. */
 ks_status ks_ctx_set_scan_algo(ks_ctx *ctx, int32_t algo);

@@ -144,6 +144,15 @@ class KmeansStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class KnnStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_select", C.c_double),
+                ("ms_merge", C.c_double), ("n_splits", C.c_int64), ("tiles_per_split", C.c_int64),
+                ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class KmeansResult(C.Structure):
     _fields_ = [("iter", C.c_int32), ("converged", C.c_int32), ("tot_withinss", C.c_double), ("totss", C.c_double)]
 
@@ -187,6 +196,7 @@ EXPORTS = [
     "ks_silhouette", "ks_silhouette_dev",
     "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
     "ks_spectra_kmeans", "ks_spectra_kmeans_dev", "ks_spectra_group_means", "ks_spectra_group_means_dev",
+    "ks_spectra_knn", "ks_spectra_knn_dev",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
     "ks_scan_chunk_indices", "ks_scan_tile_chunks",
@@ -206,6 +216,7 @@ KS_PCA_MAX_SWEEPS = 64
 KS_PCA_NO_CENTER = 1
 KS_KM_CHUNK = 256
 KS_KM_MAX_GROUPS = 65536
+KS_KNN_MAX_K = 64
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -299,6 +310,8 @@ def load():
         "ks_spectra_kmeans_dev": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P, P], I32),
         "ks_spectra_group_means": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P], I32),
         "ks_spectra_group_means_dev": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P, P], I32),
+        "ks_spectra_knn": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P], I32),
+        "ks_spectra_knn_dev": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P, P], I32),
         "ks_seq_index_create": ([P, P], I32),
         "ks_seq_index_destroy": ([P], None),
         "ks_seq_index_info_get": ([P, P], I32),
@@ -496,6 +509,17 @@ def kmeans_centers(centers, ncol: int):
         return np.ascontiguousarray(c, dtype=np.float64), None, int(c.shape[0])
     raise KmerSpansError(f"centers must be a [g, {ncol}] matrix of initial centres or a 1-d sequence of integer "
                          "row positions")
+
+
+def knn_k(k) -> tuple[int, int]:
+    """(k as the library gets it, the k the output buffers are sized by) of a
+    k argument: the library checks the range, the buffers only need a size."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise KmerSpansError(f"k must be an integer number of neighbours, not {k!r}")
+    k = int(k)
+    if not -0x80000000 <= k <= 0x7fffffff:
+        raise KmerSpansError(f"k = {k} is not an int32")
+    return k, max(1, min(k, KS_KNN_MAX_K))
 
 
 def kmeans_result(res: KmeansResult) -> dict:

@@ -393,6 +393,39 @@ def region_group_means(counts, group, ngroups=None, rows=None, device: int = 0) 
     return {"centers": cen, "size": size, "withinss": wss}
 
 
+def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device: int = 0):
+    """The k nearest regions of every region by spectrum, computed on the
+    device without the distance matrix: memory is the profile panel plus
+    O(na k), and nothing of size na x nb is written or sorted.
+
+    counts: [n, ncol] non-negative integers (uint32 range), 1 <= ncol <= 4096.
+    rows: the queries, optional integer row indices (any order, repeats
+    allowed); None = all rows.  rows_b: the candidates.  None is the self form:
+    the candidates are the queries themselves and position s is left out of its
+    own list (by position: a row named twice finds its other copy at exactly
+    0).  Otherwise every row of rows_b counts.  1 <= k <= 64, and k may not
+    exceed the number of candidates (na - 1 in the self form).  A selected row
+    without counts is an error naming its position.  The distance is
+    region_distances': squared=True returns the FP64 sum of squared profile
+    differences, otherwise its square root.  Returns (index, dist): int64
+    [na, k] positions into the candidate selection (not row indices) and
+    float64 [na, k], column 0 the nearest; the k candidates with the smallest
+    (squared distance, position), ascending, so ties go to the lowest position
+    and the same input gives the same bits on every run."""
+    c = _counts_arg(counts)
+    n, ncol = (int(v) for v in c.shape)
+    ra, rb = _rows_arg(rows, "rows"), _rows_arg(rows_b, "rows_b")
+    na = n if ra is None else int(ra.size)
+    nb = 0 if rb is None else int(rb.size)
+    k, kb = _lib.knn_k(k)
+    index = np.zeros((max(na, 0), kb), dtype=np.int64)
+    dist = np.zeros((max(na, 0), kb), dtype=np.float64)
+    check(load().ks_spectra_knn(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None, na,
+                                rb.ctypes.data if rb is not None else None, nb, k,
+                                _lib.KS_DIST_SQUARED if squared else 0, index.ctypes.data, dist.ctypes.data))
+    return index, dist
+
+
 def region_hclust(dist, method: str = "complete", device: int = 0) -> dict:
     """R's hclust() of a condensed dissimilarity vector (test.R:776), run on
     the device.

@@ -776,3 +776,40 @@ def region_group_means(ctx: _lib.Context, counts: torch.Tensor, group, ngroups=N
                                             m, g.ctypes.data, ng, 0, C.c_void_p(cen.data_ptr()), size.ctypes.data,
                                             wss.ctypes.data, C.byref(st)))
     return {"centers": cen, "size": size, "withinss": wss}, st.as_dict()
+
+
+def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=None, squared: bool = False):
+    """ks_spectra_knn_dev: the k nearest rows of a candidate selection for
+    every selected row of the spectra of region_spectra, on the device and
+    without any distance matrix (memory: the profile panel plus O(na k)).
+
+    counts: the int32 CUDA tensor [n, ncol] region_spectra returns (uint32
+    bits), used in place; 1 <= ncol <= 4096.  rows (the queries) / rows_b (the
+    candidates): optional selections of row indices, int64 CUDA tensors (used
+    in place) or numpy (uploaded); any order, repeats allowed.  rows None = all
+    rows.  rows_b None is the self form: the candidates are the queries and
+    position s is left out of its own list (by position, not by row index).
+    1 <= k <= 64, at most the number of candidates.  A selected row without
+    counts, a bad index or a k above the candidates is an error, and nothing is
+    written then.  Returns (index, dist, stats): an int64 CUDA tensor [na, k]
+    of positions into the candidate selection, a float64 CUDA tensor [na, k]
+    (the squared sum with squared=True, otherwise its root), column 0 the
+    nearest, ordered by (squared distance, position); stats the dict of
+    ks_knn_stats."""
+    dev, n, ncol = _counts_dev(counts)
+    ra = _rows_dev(rows, "rows", dev) if rows is not None else None
+    rb = _rows_dev(rows_b, "rows_b", dev) if rows_b is not None else None
+    if rb is not None and not rb.numel():
+        raise _lib.KmerSpansError("rows_b names no row")
+    na = n if ra is None else int(ra.numel())
+    nb = 0 if rb is None else int(rb.numel())
+    k, kb = _lib.knn_k(k)
+    index = torch.empty((na, kb), dtype=torch.int64, device=dev)
+    dist = torch.empty((na, kb), dtype=torch.float64, device=dev)
+    st = _lib.KnnStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    _order(ctx)
+    check(load().ks_spectra_knn_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n, ncol,
+                                    ptr(ra), na, ptr(rb), nb, k, _lib.KS_DIST_SQUARED if squared else 0,
+                                    C.c_void_p(index.data_ptr()), C.c_void_p(dist.data_ptr()), C.byref(st)))
+    return index, dist, st.as_dict()
