@@ -1230,6 +1230,119 @@ ks_status ks_spectra_group_means(ks_ctx *ctx, const uint32_t *spectra, int64_t n
                                  int32_t *size, double *withinss);
 
 /* ---------------------------------------------------------------------
+ * Starts for ks_spectra_kmeans: maximin and k-means++ seeding
+ * (csrc/ks_kmeans_seed.hip).
+ * --------------------------------------------------------------------- */
+
+/* ks_spectra_kmeans takes its initial centres from the caller.  These entries
+ * choose g rows of the selection as centres, in O(m ncol) memory and g
+ * dependent steps, each one pass "distance of every row to one centre" over
+ * the profile panel; nothing of size m x g exists.  rows_out is what init_rows
+ * of ks_spectra_kmeans_dev takes.
+ *   KS_SEED_MAXIMIN: farthest-first traversal (Gonzalez' 2-approximation of
+ *   k-centre): every pick is the row farthest from the rows picked so far.  No
+ *   random numbers; pick_dist[j] is the squared covering radius of the first j
+ *   picks, a curve over the number of groups.
+ *   KS_SEED_DSQ: k-means++ (D^2 sampling, one candidate per step).  The
+ *   uniform numbers come from the caller: the library has no generator and the
+ *   result is a function of (spectra, rows, g, first, u) alone.
+ *
+ * Input, profile and their errors: those of ks_spectra_kmeans above (n x ncol
+ * uint32 spectra, 1 <= ncol <= KS_DIST_MAX_NCOL, an optional int64 selection of
+ * m >= 1 rows in any order, repeats allowed; "row index s out of range" is
+ * reported before "row s has no counts").  1 <= g <= KS_KM_MAX_GROUPS; g > m is
+ * allowed.  Row s below is position s of the selection.
+ *
+ * Definitions, each a separate FP64 operation (no FMA):
+ *   Squared distance acc(s, r) of row s and picked row r: that of
+ *   ks_spectra_kmeans with cen = the profile of row r, bit for bit: acc = +0.0;
+ *   for c ascending: d = p[s][c] - p[r][c]; acc = acc + d * d.  It carries the
+ *   bits of ks_spectra_cross_dist(..., KS_DIST_SQUARED) for (s, r), and
+ *   acc(r, r) is exactly +0.0.
+ *   State: mind[s] = +inf and near[s] = 0 for every s.
+ *   Step j = 0 .. g - 1: a row r_j is picked (below) and rows_out[j] = r_j.
+ *   Then for every s: if acc(s, r_j) < mind[s] (strict), mind[s] = acc(s, r_j)
+ *   and near[s] = j + 1.  The lowest label keeps a tie, as in the assignment
+ *   of ks_spectra_kmeans.
+ *   Potential: pot = the chunked sum of mind over all rows: the rows in
+ *   ascending position are cut into chunks of KS_KM_CHUNK; C[c] = the chunk's
+ *   left-to-right sum from +0.0; P[0] = +0.0, P[c + 1] = P[c] + C[c];
+ *   pot = P[nchunks].  (The group sum of ks_spectra_kmeans for the single
+ *   group of all rows.)
+ *   Pick of step 0: `first` if 0 <= first < m.  first = -1 is allowed only
+ *   with KS_SEED_DSQ and means (int64)(u[0] * (double)m).  Any other first is
+ *   KS_ERR_ARG.  pick_dist[0] = potential[0] = +inf.
+ *   Pick of step j >= 1, KS_SEED_MAXIMIN: the s with the largest mind[s], the
+ *   lowest position on a tie.  pick_dist[j] = mind[s], potential[j] = pot.
+ *   Pick of step j >= 1, KS_SEED_DSQ: t = u[j] * pot (one multiplication).
+ *   c* = the first chunk with P[c* + 1] > t.  Inside it acc = +0.0 and for s
+ *   ascending acc = acc + mind[s]; the pick is the first s with
+ *   P[c*] + acc > t (one addition for the comparison).  pick_dist[j] =
+ *   mind[s], potential[j] = pot.  At the chunk's last row acc is C[c*] and
+ *   the test is P[c* + 1] > t, so a row is always found; P[c*] <= t and acc
+ *   does not move on a zero, so the picked row has mind > 0; u[j] * pot < pot
+ *   for 0 <= u[j] <= 1 - 2^-53, so the chunk exists.
+ *   Degenerate picks: when pot == +0.0 (KS_SEED_DSQ) or the largest mind is
+ *   +0.0 (KS_SEED_MAXIMIN) every row coincides with a picked one: the pick is
+ *   position 0 and pick_dist[j] = +0.0.
+ *   (pick_dist and potential of step j are taken BEFORE the update of step j.)
+ * The uniforms: u is a host array of g doubles, required with KS_SEED_DSQ and
+ * NULL with KS_SEED_MAXIMIN (u[0] is used only by first = -1).  Every entry
+ * must satisfy 0 <= u < 1, otherwise KS_ERR_ARG, "u[j] is not in [0, 1)", the
+ * first such j, before any device call.
+ * Result: n_distinct = 1 + the number of j >= 1 with pick_dist[j] > 0;
+ * potential = pot after the last step; radius and far_row = the largest mind
+ * after the last step and its lowest position: the squared covering radius,
+ * the value the next maximin pick would have had.
+ * The result is a function of the input alone, with the same bits on every
+ * run: no atomics on doubles, no reduction that depends on arrival order. */
+#define KS_SEED_MAXIMIN 0
+#define KS_SEED_DSQ 1
+typedef struct ks_seed_result {
+  int32_t n_distinct;
+  int32_t reserved;
+  double potential;
+  double radius;
+  int64_t far_row;
+} ks_seed_result;
+typedef struct ks_seed_stats { /* hipEvent times on the ctx stream, ms */
+  double ms_total;
+  double ms_normalise; /* checks and profiles, with the one read-back before the first step */
+  double ms_steps;     /* the g picks and updates and the closing reduction, queued back to back */
+  int64_t n_launches;  /* kernels launched by the call */
+  int64_t panel_bytes; /* the m x ncol FP64 profile panel */
+  int64_t work_bytes;  /* the rest of the call's one allocation: three records per chunk of 256 rows, the
+                          chunk prefix, the uniforms and the two host-bound sequences (O(g)).  Allocated and
+                          freed by the call. */
+} ks_seed_stats;
+
+/* Device-resident: spectra_dev, rows_dev, rows_out_dev (int64[g], positions
+ * into the selection), near_dev (int32[m]) and mind_dev (double[m], squared)
+ * are device pointers; u, pick_dist (double[g]), potential (double[g]) and res
+ * are host pointers.  flags: KS_SEED_MAXIMIN or KS_SEED_DSQ.  Indices and row
+ * sums are checked on the device and one read-back ends a rejected call before
+ * the first step: the outputs are untouched then and the context usable.  All
+ * other arguments are validated before any device call.  The g steps are
+ * queued without a host round trip; one read-back at the end brings pick_dist,
+ * potential and the result.  The only allocation is the work memory counted in
+ * panel_bytes + work_bytes (KS_ERR_NOMEM if it fails), freed before return.
+ * stats may be NULL.  ctx == NULL is the default context on device 0; the
+ * calls are never spread over a device list and are not forwarded by the fork
+ * broker. */
+ks_status ks_spectra_kmeans_seed_dev(ks_ctx *ctx, const uint32_t *spectra_dev, int64_t n, int32_t ncol,
+                                     const int64_t *rows_dev, int64_t m, int32_t g, int32_t flags, int64_t first,
+                                     const double *u, int64_t *rows_out_dev, int32_t *near_dev, double *mind_dev,
+                                     double *pick_dist, double *potential, ks_seed_result *res,
+                                     ks_seed_stats *stats);
+/* Host buffers: validates every argument, every index and every row sum before
+ * any device call, then uploads, runs the device entry and copies the results
+ * back. */
+ks_status ks_spectra_kmeans_seed(ks_ctx *ctx, const uint32_t *spectra, int64_t n, int32_t ncol, const int64_t *rows,
+                                 int64_t m, int32_t g, int32_t flags, int64_t first, const double *u,
+                                 int64_t *rows_out, int32_t *near, double *mind, double *pick_dist,
+                                 double *potential, ks_seed_result *res);
+
+/* ---------------------------------------------------------------------
  * k nearest regions by spectrum, without the distance matrix
  * (csrc/ks_knn.hip).
  * --------------------------------------------------------------------- */

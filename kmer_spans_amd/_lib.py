@@ -157,6 +157,19 @@ class KmeansResult(C.Structure):
     _fields_ = [("iter", C.c_int32), ("converged", C.c_int32), ("tot_withinss", C.c_double), ("totss", C.c_double)]
 
 
+class SeedResult(C.Structure):
+    _fields_ = [("n_distinct", C.c_int32), ("reserved", C.c_int32), ("potential", C.c_double),
+                ("radius", C.c_double), ("far_row", C.c_int64)]
+
+
+class SeedStats(C.Structure):
+    _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_steps", C.c_double),
+                ("n_launches", C.c_int64), ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class Fasta(C.Structure):
     _fields_ = [("seqs", DevSeqs), ("names", C.POINTER(C.c_char_p)), ("n_records", C.c_int64),
                 ("bases_all", C.c_int64), ("bases_kept", C.c_int64), ("device", C.c_int32),
@@ -196,6 +209,7 @@ EXPORTS = [
     "ks_silhouette", "ks_silhouette_dev",
     "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
     "ks_spectra_kmeans", "ks_spectra_kmeans_dev", "ks_spectra_group_means", "ks_spectra_group_means_dev",
+    "ks_spectra_kmeans_seed", "ks_spectra_kmeans_seed_dev",
     "ks_spectra_knn", "ks_spectra_knn_dev",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
@@ -217,6 +231,7 @@ KS_PCA_NO_CENTER = 1
 KS_KM_CHUNK = 256
 KS_KM_MAX_GROUPS = 65536
 KS_KNN_MAX_K = 64
+SEED_METHODS = {"maximin": 0, "kmeans++": 1}  # KS_SEED_MAXIMIN, KS_SEED_DSQ
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
@@ -310,6 +325,8 @@ def load():
         "ks_spectra_kmeans_dev": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P, P], I32),
         "ks_spectra_group_means": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P], I32),
         "ks_spectra_group_means_dev": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P, P], I32),
+        "ks_spectra_kmeans_seed": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P], I32),
+        "ks_spectra_kmeans_seed_dev": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P, P], I32),
         "ks_spectra_knn": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P], I32),
         "ks_spectra_knn_dev": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P, P], I32),
         "ks_seq_index_create": ([P, P], I32),
@@ -520,6 +537,48 @@ def knn_k(k) -> tuple[int, int]:
     if not -0x80000000 <= k <= 0x7fffffff:
         raise KmerSpansError(f"k = {k} is not an int32")
     return k, max(1, min(k, KS_KNN_MAX_K))
+
+
+def seed_args(g, method, first, u, seed):
+    """(g, the g the buffers are sized by, flags, first, u float64[g] or None)
+    of the arguments of region_kmeans_seed.  The library checks the ranges of
+    g, first and u; a seed is turned into np.random.default_rng(seed).random(g)
+    here, so the library itself draws nothing."""
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+        raise KmerSpansError(f"g must be an integer number of centres, not {g!r}")
+    g = int(g)
+    if not -0x80000000 <= g <= 0x7fffffff:
+        raise KmerSpansError(f"g = {g} is not an int32")
+    gb = max(1, min(g, KS_KM_MAX_GROUPS))
+    if method not in SEED_METHODS:
+        raise KmerSpansError(f"method must be one of {sorted(SEED_METHODS)}, not {method!r}")
+    flags = SEED_METHODS[method]
+    if flags == 0:
+        if u is not None or seed is not None:
+            raise KmerSpansError("method='maximin' draws nothing: u and seed must be None")
+        if first is None:
+            raise KmerSpansError("method='maximin' needs a first row (first=None is a drawn row of 'kmeans++')")
+    else:
+        if (u is None) == (seed is None):
+            raise KmerSpansError("method='kmeans++' needs exactly one of u (g uniform numbers in [0, 1)) and seed")
+        if u is None:
+            u = np.random.default_rng(seed).random(gb)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 1 or u.size != gb:
+            raise KmerSpansError(f"u must hold g = {g} numbers")
+    if first is None:
+        first = -1
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)):
+        raise KmerSpansError(f"first must be an integer row position or None, not {first!r}")
+    first = int(first)
+    if not -0x8000000000000000 <= first <= 0x7fffffffffffffff:
+        raise KmerSpansError(f"first = {first} is not an int64")
+    return g, gb, flags, first, u
+
+
+def seed_result(res: SeedResult) -> dict:
+    return {"n_distinct": int(res.n_distinct), "potential_final": float(res.potential), "radius": float(res.radius),
+            "far_row": int(res.far_row)}
 
 
 def kmeans_result(res: KmeansResult) -> dict:

@@ -341,8 +341,8 @@ def region_kmeans(counts, centers, rows=None, iter_max: int = 10, device: int = 
     rows.  A row's profile is counts / row sum; a selected row without counts
     is an error naming its position.  centers: a [g, ncol] float matrix of
     initial centres (every entry finite), or a 1-d sequence of g integer
-    positions into the selection whose profiles are the initial centres.  No
-    random start is offered: the caller draws the positions.  Duplicate centres
+    positions into the selection whose profiles are the initial centres
+    (region_kmeans_seed chooses such positions).  Duplicate centres
     are allowed; the lowest label wins every tie.  1 <= g <= 65536.  Returns
     {'cluster': int32[m] labels 1 .. g, 'centers': float64[g, ncol], 'size':
     int32[g], 'withinss': float64[g], 'tot_withinss', 'totss', 'betweenss'
@@ -391,6 +391,50 @@ def region_group_means(counts, group, ngroups=None, rows=None, device: int = 0) 
     check(load().ks_spectra_group_means(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None,
                                         m, g.ctypes.data, ng, 0, cen.ctypes.data, size.ctypes.data, wss.ctypes.data))
     return {"centers": cen, "size": size, "withinss": wss}
+
+
+def region_kmeans_seed(counts, g, method: str = "maximin", rows=None, first=0, u=None, seed=None,
+                       device: int = 0) -> dict:
+    """g rows of the selection to start region_kmeans from, chosen on the
+    device in O(m ncol) memory: no distance matrix and nothing of size m x g.
+
+    counts, rows: as for region_kmeans.  method="maximin": farthest-first
+    traversal from row `first`; every later pick is the row farthest from the
+    rows picked so far (the lowest position on a tie).  Nothing is drawn, and
+    'pick_dist' is the squared covering radius as a function of the number of
+    centres: where it flattens, more groups buy little.  method="kmeans++": D^2
+    sampling; pick j is drawn with probability proportional to the squared
+    distance to the nearest earlier pick, from the uniform number u[j].  Give u
+    (g numbers in [0, 1)) or seed; with seed, u is
+    np.random.default_rng(seed).random(g), drawn here: the library has no
+    generator.  first=None (k-means++ only) draws the first row as
+    int(u[0] * m).  1 <= g <= 65536; g > m is allowed (the surplus picks repeat
+    position 0 at distance 0).  Returns {'rows': int64[g] positions into the
+    selection (region_kmeans(..., centers=res['rows'])), 'nearest': int32[m]
+    the 1-based pick nearest to every row (the lowest on a tie), 'mindist':
+    float64[m] its squared distance, 'pick_dist': float64[g] the squared
+    distance of every pick to the earlier picks (inf for the first),
+    'potential': float64[g] the sum of mindist before every pick (inf for the
+    first), 'n_distinct': picks that differ from all earlier ones,
+    'potential_final', 'radius' and 'far_row': the sum and the largest mindist
+    after the last pick and its row}.  Every value is a fixed order of FP64
+    operations (include/kmer_spans.h): the same input gives the same bits on
+    every run."""
+    c = _counts_arg(counts)
+    n, ncol = (int(v) for v in c.shape)
+    r = _rows_arg(rows, "rows")
+    m = n if r is None else int(r.size)
+    g, gb, flags, first, u = _lib.seed_args(g, method, first, u, seed)
+    picked = np.zeros(gb, dtype=np.int64)
+    near, mind = np.zeros(max(m, 0), dtype=np.int32), np.zeros(max(m, 0), dtype=np.float64)
+    pd, pot = np.zeros(gb, dtype=np.float64), np.zeros(gb, dtype=np.float64)
+    res = _lib.SeedResult()
+    check(load().ks_spectra_kmeans_seed(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None,
+                                        m, g, flags, first, u.ctypes.data if u is not None else None,
+                                        picked.ctypes.data, near.ctypes.data, mind.ctypes.data, pd.ctypes.data,
+                                        pot.ctypes.data, C.byref(res)))
+    return dict({"rows": picked, "nearest": near, "mindist": mind, "pick_dist": pd, "potential": pot},
+                **_lib.seed_result(res))
 
 
 def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device: int = 0):

@@ -778,6 +778,42 @@ def region_group_means(ctx: _lib.Context, counts: torch.Tensor, group, ngroups=N
     return {"centers": cen, "size": size, "withinss": wss}, st.as_dict()
 
 
+def region_kmeans_seed(ctx: _lib.Context, counts: torch.Tensor, g, method: str = "maximin", rows=None, first=0,
+                       u=None, seed=None):
+    """ks_spectra_kmeans_seed_dev: g rows of the selection to start
+    region_kmeans from, by maximin (farthest-first) or k-means++ (D^2
+    sampling), on the device in O(m ncol) memory.
+
+    counts, rows: as for region_kmeans.  g, method, first, u, seed: as for
+    api.region_kmeans_seed (u is a host array: the library reads it before any
+    device call).  A selected row without counts or a bad index is an error
+    naming its position, and nothing is written then.  Returns (res, stats):
+    res is a dict of 'rows' (int64 CUDA tensor [g], positions into the
+    selection: region_kmeans(ctx, counts, centers=res['rows'], rows=rows)),
+    'nearest' (int32 CUDA tensor [m]), 'mindist' (float64 CUDA tensor [m],
+    squared), 'pick_dist' and 'potential' (float64 numpy [g]) and the scalars
+    'n_distinct', 'potential_final', 'radius', 'far_row'; stats the dict of
+    ks_seed_stats.  The g steps are queued without a host round trip."""
+    dev, n, ncol = _counts_dev(counts)
+    r = _rows_dev(rows, "rows", dev) if rows is not None else None
+    m = n if r is None else int(r.numel())
+    g, gb, flags, first, u = _lib.seed_args(g, method, first, u, seed)
+    picked = torch.empty(gb, dtype=torch.int64, device=dev)
+    near = torch.empty(m, dtype=torch.int32, device=dev)
+    mind = torch.empty(m, dtype=torch.float64, device=dev)
+    pd, pot = np.zeros(gb, dtype=np.float64), np.zeros(gb, dtype=np.float64)
+    out, st = _lib.SeedResult(), _lib.SeedStats()
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    _order(ctx)
+    check(load().ks_spectra_kmeans_seed_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n,
+                                            ncol, ptr(r), m, g, flags, first, u.ctypes.data if u is not None else None,
+                                            ptr(picked), ptr(near), ptr(mind), pd.ctypes.data, pot.ctypes.data,
+                                            C.byref(out), C.byref(st)))
+    res = dict({"rows": picked, "nearest": near, "mindist": mind, "pick_dist": pd, "potential": pot},
+               **_lib.seed_result(out))
+    return res, st.as_dict()
+
+
 def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=None, squared: bool = False):
     """ks_spectra_knn_dev: the k nearest rows of a candidate selection for
     every selected row of the spectra of region_spectra, on the device and
