@@ -253,13 +253,6 @@ __global__ void __launch_bounds__(kHcThreads) k_hclust_rescan(const double *d, i
   }
 }
 
-struct DevFree {  // the copy goes back before the call returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // ------------------------------------------------------------------- host
 
 // ia / ib (0-based rows, a < b; the cluster keeps a's row) -> R's merge and order.
@@ -318,13 +311,7 @@ ks_status hclust_impl(ks_ctx *ctx, double *diss, int64_t n, int method, int flag
   DevFree copy;
   double *d = diss;
   if (flags & KS_HCLUST_KEEP_INPUT) {
-    hipError_t e = hipMalloc(&copy.p, (size_t)total * 8);
-    if (e != hipSuccess) {
-      copy.p = nullptr;
-      (void)hipGetLastError();
-      return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the copy of the dissimilarities failed: %s", (size_t)total * 8,
-                  hipGetErrorString(e));
-    }
+    KS_TRY(dev_alloc(&copy, (size_t)total * 8, "the copy of the dissimilarities"));
     d = static_cast<double *>(copy.p);
   }
   KS_HIP(hipEventRecord(ctx->ev[2], st));
@@ -356,15 +343,10 @@ ks_status hclust_impl(ks_ctx *ctx, double *diss, int64_t n, int method, int flag
     return fail(KS_ERR_ARG, "no finite dissimilarity was left to merge: the averages overflowed");
   merge_and_order(iab.data(), iab.data() + n, n, merge, order);
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_check = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_init = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    stats->ms_merge = ms;
+    KS_TRY(event_ms(ctx, 0, 4, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_check));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_init));
+    KS_TRY(event_ms(ctx, 3, 4, &stats->ms_merge));
     stats->n = n;
     stats->n_rescans = (int64_t)tail[0];
     stats->work_bytes = copy.p ? total * 8 : 0;

@@ -302,6 +302,40 @@ ks_status ensure(ks_ctx *ctx, Slot s, size_t bytes, void **out);
 void debug_poison(void *p, size_t n);
 void debug_poison_workspace(ks_ctx *ctx);
 ks_status ensure_pinned(ks_ctx *ctx, size_t bytes, void **out);
+// A call's own device allocation: it goes back before the call returns, whichever way it ends.
+struct DevFree {
+  void *p = nullptr;
+  ~DevFree() {
+    if (p) (void)hipFree(p);
+  }
+};
+inline ks_status dev_alloc(DevFree *f, size_t bytes, const char *what) {
+  const hipError_t e = hipMalloc(&f->p, bytes);
+  if (e != hipSuccess) {
+    f->p = nullptr;
+    (void)hipGetLastError();
+    return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for %s failed: %s", bytes, what, hipGetErrorString(e));
+  }
+  return KS_OK;
+}
+// One allocation cut into pieces that start on 256-byte boundaries.  base null: only the sizes (off).
+struct Arena {
+  char *base = nullptr;
+  size_t off = 0;
+  template <class T>
+  T *take(size_t count) {
+    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+    off += (count * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+};
+// Milliseconds between two recorded events of the context (the stage times of the stats).
+inline ks_status event_ms(ks_ctx *ctx, int from, int to, double *ms) {
+  float f = 0;
+  KS_HIP(hipEventElapsedTime(&f, ctx->ev[from], ctx->ev[to]));
+  *ms = f;
+  return KS_OK;
+}
 // Host sequences staged on the device for a host entry point (ks_stage.cpp).
 struct Staged {
   ks_dev_seqs dev{};

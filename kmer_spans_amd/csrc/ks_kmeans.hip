@@ -14,12 +14,11 @@
 // over a group takes its members in ascending position order, cut into chunks
 // of KS_KM_CHUNK, a partial per chunk, the partials added in chunk order.
 //
-// Normalise: k_km_normalise, a wave per selected row: the index is checked, the
-//            row summed in uint64 and p = cnt / T written to the ROW-MAJOR panel
-//            [m][ncol] (the update reads whole member rows).  Bad indices, empty
-//            rows, non-finite centres and bad initial rows are recorded with
-//            integer atomicMax (the first position wins) and one 32-byte
-//            read-back ends the call before any output is written.
+// Normalise: the shared row-major profile panel [m][ncol] (ks_panel.hip; the
+//            update reads whole member rows).  Non-finite centres and bad
+//            initial rows are recorded beside the panel's own two words, in the
+//            same way, and one 32-byte read-back ends the call before any
+//            output is written.
 // Assign:    k_km_assign: a block of 256 threads keeps 64 rows and walks centre
 //            tiles of 64, a thread a 4 x 4 register block of accumulators as in
 //            k_dist_tile; chunks of 16 columns of both are staged in LDS,
@@ -50,7 +49,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ks_internal.h"
-#include "ks_km_common.h"
+#include "ks_panel.h"
 
 namespace ks {
 namespace {
@@ -63,7 +62,12 @@ constexpr int kFoldBatch = 8;
 
 enum FoldMode : int { kFoldMeanKeep = 0, kFoldMeanNan = 1, kFoldSum = 2 };
 
-// KmState and k_km_normalise: ks_km_common.h
+struct KmState {
+  // cnt - position of the first bad row index / empty row / non-finite centre entry / bad initial row (0: none)
+  unsigned long long bad[4];
+  int changed;
+  int pad;
+};
 
 __global__ void __launch_bounds__(256) k_km_check_init(const double *__restrict__ init, int64_t total,
                                                        KmState *__restrict__ state) {
@@ -334,35 +338,29 @@ struct KmWork {
   int64_t max_chunks = 0;
   int nsplit = 1, tps = 1;
 
-  static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
   // base null: only the sizes
   void lay(char *base, int64_t m, int ncol, int g) {
-    size_t o = 0;
-    auto take = [&](size_t b) {
-      char *p = base ? base + o : nullptr;
-      o += up(b);
-      return p;
-    };
-    panel = reinterpret_cast<double *>(take((size_t)m * ncol * 8));
-    panel_bytes = o;
-    part = reinterpret_cast<double *>(take((size_t)max_chunks * ncol * 8));
-    dval = reinterpret_cast<double *>(take((size_t)m * 8));
-    wpart = reinterpret_cast<double *>(take((size_t)max_chunks * 8));
-    wss = reinterpret_cast<double *>(take((size_t)g * 8));
-    tcen = reinterpret_cast<double *>(take((size_t)ncol * 8));
-    tot = reinterpret_cast<double *>(take(8));
-    pval = reinterpret_cast<double *>(take((size_t)nsplit * m * 8));
-    plab = reinterpret_cast<int *>(take((size_t)nsplit * m * 4));
-    skeys = reinterpret_cast<int *>(take((size_t)m * 4));
-    perm = reinterpret_cast<int *>(take((size_t)m * 4));
-    iota = reinterpret_cast<int *>(take((size_t)m * 4));
-    lab = reinterpret_cast<int *>(take((size_t)m * 4));
-    gstart = reinterpret_cast<int *>(take((size_t)(g + 1) * 4));
-    cbase = reinterpret_cast<int *>(take((size_t)(g + 1) * 4));
-    one = reinterpret_cast<int *>(take(4 * 4));
-    state = reinterpret_cast<KmState *>(take(sizeof(KmState)));
-    sort_tmp = take(sort_bytes);
-    bytes = o;
+    Arena a{base};
+    panel = a.take<double>((size_t)m * ncol);
+    panel_bytes = a.off;
+    part = a.take<double>((size_t)max_chunks * ncol);
+    dval = a.take<double>((size_t)m);
+    wpart = a.take<double>((size_t)max_chunks);
+    wss = a.take<double>((size_t)g);
+    tcen = a.take<double>((size_t)ncol);
+    tot = a.take<double>(1);
+    pval = a.take<double>((size_t)nsplit * m);
+    plab = a.take<int>((size_t)nsplit * m);
+    skeys = a.take<int>((size_t)m);
+    perm = a.take<int>((size_t)m);
+    iota = a.take<int>((size_t)m);
+    lab = a.take<int>((size_t)m);
+    gstart = a.take<int>((size_t)(g + 1));
+    cbase = a.take<int>((size_t)(g + 1));
+    one = a.take<int>(4);
+    state = a.take<KmState>(1);
+    sort_tmp = a.take<char>(sort_bytes);
+    bytes = a.off;
   }
 };
 
@@ -390,12 +388,7 @@ ks_status km_alloc(ks_ctx *ctx, int64_t m, int ncol, int g, bool assign, KmWork 
                                             (const int *)nullptr, (int *)nullptr, (int)m, 0, bits_for(g),
                                             ctx->stream));
   w->lay(nullptr, m, ncol, g);
-  const hipError_t e = hipMalloc(&mem->p, w->bytes);
-  if (e != hipSuccess) {
-    mem->p = nullptr;
-    (void)hipGetLastError();
-    return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the profile panel failed: %s", w->bytes, hipGetErrorString(e));
-  }
+  KS_TRY(dev_alloc(mem, w->bytes, "the profile panel"));
   w->lay(static_cast<char *>(mem->p), m, ncol, g);
   return KS_OK;
 }
@@ -405,9 +398,7 @@ ks_status km_normalise(ks_ctx *ctx, const KmWork &w, const uint32_t *sp, int64_t
                        int64_t m, const double *init, const int64_t *init_rows, int g) {
   hipStream_t st = ctx->stream;
   KS_HIP(hipMemsetAsync(w.state, 0, sizeof(KmState), st));
-  hipLaunchKernelGGL(k_km_normalise, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, sp, n, ncol, rows, m, w.panel,
-                     w.iota, w.state);
-  KS_HIP(hipGetLastError());
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, w.panel, w.iota, &w.state->bad[0], &w.state->bad[1]));
   if (init) {
     const int64_t total = (int64_t)g * ncol;
     const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cus * 8);
@@ -422,8 +413,7 @@ ks_status km_normalise(ks_ctx *ctx, const KmWork &w, const uint32_t *sp, int64_t
   unsigned long long hbad[4] = {0, 0, 0, 0};
   KS_HIP(hipMemcpyAsync(hbad, w.state->bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
-  if (hbad[0]) return fail(KS_ERR_ARG, "row index %lld out of range", (long long)(m - (int64_t)hbad[0]));
-  if (hbad[1]) return fail(KS_ERR_ARG, "row %lld has no counts", (long long)(m - (int64_t)hbad[1]));
+  KS_TRY(panel_report(hbad, 1, m, 0));
   if (hbad[2]) {
     const int64_t at = (int64_t)g * ncol - (int64_t)hbad[2];
     return fail(KS_ERR_ARG, "center[%lld][%lld] is not finite", (long long)(at / ncol), (long long)(at % ncol));
@@ -481,7 +471,7 @@ ks_status km_download(ks_ctx *ctx, const KmWork &w, int g, int32_t *size, double
 ks_status check_kmeans_args(const void *spectra, int64_t n, int32_t ncol, const void *rows, int64_t m, const void *init,
                             const void *init_rows, int32_t g, int32_t iter_max, int32_t flags, const void *cluster,
                             const void *centers, const void *size, const void *withinss, const void *res) {
-  KS_TRY(check_km_common(n, ncol, rows, m, flags, "a k-means call"));
+  KS_TRY(panel_check_common(n, ncol, rows, m, flags, "a k-means call"));
   if (g < 1 || g > KS_KM_MAX_GROUPS)
     return fail(KS_ERR_ARG, "the number of groups must be between 1 and %d (g = %d)", KS_KM_MAX_GROUPS, (int)g);
   if (iter_max < 1) return fail(KS_ERR_ARG, "iter_max = %d is not positive", (int)iter_max);
@@ -497,7 +487,7 @@ ks_status check_kmeans_args(const void *spectra, int64_t n, int32_t ncol, const 
 ks_status check_means_args(const void *spectra, int64_t n, int32_t ncol, const void *rows, int64_t m,
                            const int32_t *group, int32_t ngroups, int32_t flags, const void *centers, int32_t *size,
                            const void *withinss) {
-  KS_TRY(check_km_common(n, ncol, rows, m, flags, "a group-means call"));
+  KS_TRY(panel_check_common(n, ncol, rows, m, flags, "a group-means call"));
   if (ngroups < 1 || ngroups > KS_KM_MAX_GROUPS)
     return fail(KS_ERR_ARG, "ngroups = %d is not in 1 .. %d", (int)ngroups, KS_KM_MAX_GROUPS);
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
@@ -548,13 +538,13 @@ ks_status kmeans_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, cons
     int changed = 0;
     KS_HIP(hipMemcpyAsync(&changed, &w.state->changed, 4, hipMemcpyDeviceToHost, st));
     KS_HIP(hipStreamSynchronize(st));  // the pass's one round trip
-    float ms = 0;
+    double ms = 0;
     if (update_pending) {
-      KS_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+      KS_TRY(event_ms(ctx, 4, 5, &ms));
       ms_update += ms;
       update_pending = false;
     }
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+    KS_TRY(event_ms(ctx, 2, 3, &ms));
     ms_assign += ms;
     iter = it;
     if (changed == 0) {
@@ -592,17 +582,14 @@ ks_status kmeans_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, cons
   res->tot_withinss = tw;
   res->totss = totss;
   if (stats) {
-    float ms = 0;
     if (update_pending) {
-      KS_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+      double ms = 0;
+      KS_TRY(event_ms(ctx, 4, 5, &ms));
       ms_update += ms;
     }
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[7]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
-    stats->ms_wss = ms;
+    KS_TRY(event_ms(ctx, 0, 7, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 6, 7, &stats->ms_wss));
     stats->ms_assign = ms_assign;
     stats->ms_update = ms_update;
     stats->n_iter = iter;
@@ -632,15 +619,10 @@ ks_status means_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const
   KS_HIP(hipEventRecord(ctx->ev[3], st));
   KS_TRY(km_download(ctx, w, g, size, withinss));
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-    stats->ms_update = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_wss = ms;
+    KS_TRY(event_ms(ctx, 0, 3, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 1, 2, &stats->ms_update));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_wss));
     stats->panel_bytes = (int64_t)w.panel_bytes;
     stats->work_bytes = (int64_t)(w.bytes - w.panel_bytes);
   }
@@ -672,7 +654,7 @@ extern "C" ks_status ks_spectra_kmeans(ks_ctx *ctx, const uint32_t *spectra, int
                                        int32_t *size, double *withinss, ks_kmeans_result *res) {
   KS_TRY(check_kmeans_args(spectra, n, ncol, rows, m, init, init_rows, g, iter_max, flags, cluster, centers, size,
                            withinss, res));
-  KS_TRY(check_rows_and_sums_host(spectra, n, ncol, rows, m));
+  KS_TRY(panel_check_rows_host(spectra, n, ncol, rows, m, nullptr, 0));
   if (init) {
     for (int64_t i = 0; i < (int64_t)g * ncol; ++i)
       if (!std::isfinite(init[i]))
@@ -685,28 +667,23 @@ extern "C" ks_status ks_spectra_kmeans(ks_ctx *ctx, const uint32_t *spectra, int
   KS_TRY(default_ctx(&ctx));
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
+  void *d_out = nullptr;
   const size_t cen_bytes = (size_t)g * ncol * 8;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(m + g + 1) * 8, &d_rows));
   KS_TRY(ensure(ctx, SLOT_REG_TMP, cen_bytes + (size_t)m * 4, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, spectra, n, ncol, rows, m, nullptr, 0, g, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, spectra, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_r = nullptr, *d_ir = nullptr;
-  if (rows) {
-    d_r = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_r, rows, (size_t)m * 8, hipMemcpyHostToDevice, st));
-  }
+  int64_t *d_ir = nullptr;
   double *d_cen = static_cast<double *>(d_out);
   int *d_cl = reinterpret_cast<int *>(static_cast<char *>(d_out) + cen_bytes);
   if (init) {  // the initial centres go up into the output buffer: the device entry allows the alias
     KS_HIP(hipMemcpyAsync(d_cen, init, cen_bytes, hipMemcpyHostToDevice, st));
   } else {
-    d_ir = static_cast<int64_t *>(d_rows) + m;
+    d_ir = up.extra;
     KS_HIP(hipMemcpyAsync(d_ir, init_rows, (size_t)g * 8, hipMemcpyHostToDevice, st));
   }
-  KS_TRY(kmeans_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_r, m, init ? d_cen : nullptr, d_ir, g,
-                     iter_max, d_cl, d_cen, size, withinss, res, nullptr));
+  KS_TRY(kmeans_impl(ctx, up.sp, n, ncol, up.rows, m, init ? d_cen : nullptr, d_ir, g, iter_max, d_cl, d_cen, size,
+                     withinss, res, nullptr));
   KS_HIP(hipMemcpyAsync(centers, d_cen, cen_bytes, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(cluster, d_cl, (size_t)m * 4, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
@@ -728,24 +705,18 @@ extern "C" ks_status ks_spectra_group_means(ks_ctx *ctx, const uint32_t *spectra
                                             const int64_t *rows, int64_t m, const int32_t *group, int32_t ngroups,
                                             int32_t flags, double *centers, int32_t *size, double *withinss) {
   KS_TRY(check_means_args(spectra, n, ncol, rows, m, group, ngroups, flags, centers, size, withinss));
-  KS_TRY(check_rows_and_sums_host(spectra, n, ncol, rows, m));
+  KS_TRY(panel_check_rows_host(spectra, n, ncol, rows, m, nullptr, 0));
   KS_TRY(default_ctx(&ctx));
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
+  void *d_out = nullptr;
   const size_t cen_bytes = (size_t)ngroups * ncol * 8;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(m + 1) * 8, &d_rows));
   KS_TRY(ensure(ctx, SLOT_REG_TMP, cen_bytes, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, spectra, n, ncol, rows, m, nullptr, 0, 0, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, spectra, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_r = nullptr;
-  if (rows) {
-    d_r = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_r, rows, (size_t)m * 8, hipMemcpyHostToDevice, st));
-  }
-  KS_TRY(means_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_r, m, group, ngroups,
-                    static_cast<double *>(d_out), size, withinss, nullptr));
+  KS_TRY(means_impl(ctx, up.sp, n, ncol, up.rows, m, group, ngroups, static_cast<double *>(d_out), size, withinss,
+                    nullptr));
   KS_HIP(hipMemcpyAsync(centers, d_out, cen_bytes, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
   return KS_OK;

@@ -4,8 +4,7 @@
 // include/kmer_spans.h.
 //
 // g dependent steps, each one pass "distance of every row to one centre" over
-// the row-major FP64 profile panel of ks_kmeans.hip (k_km_normalise,
-// ks_km_common.h).  Memory is O(m ncol); nothing of size m x g exists.  Every
+// the shared row-major FP64 profile panel (ks_panel.hip).  Memory is O(m ncol); nothing of size m x g exists.  Every
 // value is a fixed order of separate FP64 operations (-ffp-contract=off,
 // csrc/Makefile).
 //
@@ -39,7 +38,7 @@
 #include <vector>
 
 #include "ks_internal.h"
-#include "ks_km_common.h"
+#include "ks_panel.h"
 
 namespace ks {
 namespace {
@@ -260,30 +259,24 @@ struct SeedWork {
   double *panel, *csum, *cmax, *P, *ud, *pd, *potv;
   int *cpos;
   SeedHead *head;  // head, pd [g], potv [g] are contiguous: one copy brings them back
-  KmState *state;
+  unsigned long long *bad;  // the panel's two words: first bad row index, first empty row
   size_t panel_bytes = 0, bytes = 0;
 
-  static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
   // base null: only the sizes
   void lay(char *base, int64_t m, int ncol, int g, int nch) {
-    size_t o = 0;
-    auto take = [&](size_t b) {
-      char *p = base ? base + o : nullptr;
-      o += up(b);
-      return p;
-    };
-    panel = reinterpret_cast<double *>(take((size_t)m * ncol * 8));
-    panel_bytes = o;
-    csum = reinterpret_cast<double *>(take((size_t)nch * 8));
-    cmax = reinterpret_cast<double *>(take((size_t)nch * 8));
-    cpos = reinterpret_cast<int *>(take((size_t)nch * 4));
-    P = reinterpret_cast<double *>(take((size_t)(nch + 1) * 8));
-    ud = reinterpret_cast<double *>(take((size_t)g * 8));
-    head = reinterpret_cast<SeedHead *>(take(sizeof(SeedHead) + (size_t)g * 16));
+    Arena a{base};
+    panel = a.take<double>((size_t)m * ncol);
+    panel_bytes = a.off;
+    csum = a.take<double>((size_t)nch);
+    cmax = a.take<double>((size_t)nch);
+    cpos = a.take<int>((size_t)nch);
+    P = a.take<double>((size_t)(nch + 1));
+    ud = a.take<double>((size_t)g);
+    head = reinterpret_cast<SeedHead *>(a.take<char>(sizeof(SeedHead) + (size_t)g * 16));
     pd = reinterpret_cast<double *>(reinterpret_cast<char *>(head) + sizeof(SeedHead));
     potv = pd + g;
-    state = reinterpret_cast<KmState *>(take(sizeof(KmState)));
-    bytes = o;
+    bad = a.take<unsigned long long>(2);
+    bytes = a.off;
   }
 };
 
@@ -291,7 +284,7 @@ struct SeedWork {
 ks_status check_seed_args(const void *spectra, int64_t n, int32_t ncol, const void *rows, int64_t m, int32_t g,
                           int32_t flags, int64_t first, const double *u, const void *rows_out, const void *near,
                           const void *mind, const void *pick_dist, const void *potential, const void *res) {
-  KS_TRY(check_km_common(n, ncol, rows, m, 0, "a seeding call"));
+  KS_TRY(panel_check_common(n, ncol, rows, m, 0, "a seeding call"));
   if (g < 1 || g > KS_KM_MAX_GROUPS)
     return fail(KS_ERR_ARG, "the number of groups must be between 1 and %d (g = %d)", KS_KM_MAX_GROUPS, (int)g);
   if (flags != KS_SEED_MAXIMIN && flags != KS_SEED_DSQ)
@@ -321,24 +314,16 @@ ks_status seed_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   SeedWork w;
   DevFree mem;
   w.lay(nullptr, m, ncol, g, nch);
-  const hipError_t e = hipMalloc(&mem.p, w.bytes);
-  if (e != hipSuccess) {
-    mem.p = nullptr;
-    (void)hipGetLastError();
-    return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the profile panel failed: %s", w.bytes, hipGetErrorString(e));
-  }
+  KS_TRY(dev_alloc(&mem, w.bytes, "the profile panel"));
   w.lay(static_cast<char *>(mem.p), m, ncol, g, nch);
   KS_HIP(hipEventRecord(ctx->ev[0], st));
-  KS_HIP(hipMemsetAsync(w.state, 0, sizeof(KmState), st));
-  hipLaunchKernelGGL(k_km_normalise, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, sp, n, ncol, rows, m, w.panel,
-                     (int *)nullptr, w.state);
-  KS_HIP(hipGetLastError());
+  KS_HIP(hipMemsetAsync(w.bad, 0, 16, st));
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, w.panel, nullptr, &w.bad[0], &w.bad[1]));
   if (dsq) KS_HIP(hipMemcpyAsync(w.ud, u, (size_t)g * 8, hipMemcpyHostToDevice, st));
   unsigned long long hbad[2] = {0, 0};
-  KS_HIP(hipMemcpyAsync(hbad, w.state->bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
+  KS_HIP(hipMemcpyAsync(hbad, w.bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
-  if (hbad[0]) return fail(KS_ERR_ARG, "row index %lld out of range", (long long)(m - (int64_t)hbad[0]));
-  if (hbad[1]) return fail(KS_ERR_ARG, "row %lld has no counts", (long long)(m - (int64_t)hbad[1]));
+  KS_TRY(panel_report(hbad, 1, m, 0));
   // from here on the outputs are written
   KS_HIP(hipEventRecord(ctx->ev[1], st));
   for (int j = 0; j <= g; ++j) {
@@ -365,13 +350,9 @@ ks_status seed_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   res->radius = head.radius;
   res->far_row = head.far_row;
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[2]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-    stats->ms_steps = ms;
+    KS_TRY(event_ms(ctx, 0, 2, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 1, 2, &stats->ms_steps));
     stats->n_launches = 2 + 2 * (int64_t)g;
     stats->panel_bytes = (int64_t)w.panel_bytes;
     stats->work_bytes = (int64_t)(w.bytes - w.panel_bytes);
@@ -404,26 +385,20 @@ extern "C" ks_status ks_spectra_kmeans_seed(ks_ctx *ctx, const uint32_t *spectra
                                             double *pick_dist, double *potential, ks_seed_result *res) {
   KS_TRY(check_seed_args(spectra, n, ncol, rows, m, g, flags, first, u, rows_out, near, mind, pick_dist, potential,
                          res));
-  KS_TRY(check_rows_and_sums_host(spectra, n, ncol, rows, m));
+  KS_TRY(panel_check_rows_host(spectra, n, ncol, rows, m, nullptr, 0));
   KS_TRY(default_ctx(&ctx));
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(m + g + 1) * 8, &d_rows));
+  void *d_out = nullptr;
   KS_TRY(ensure(ctx, SLOT_REG_TMP, (size_t)m * 12, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, spectra, n, ncol, rows, m, nullptr, 0, g, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, spectra, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_r = nullptr;
-  if (rows) {
-    d_r = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_r, rows, (size_t)m * 8, hipMemcpyHostToDevice, st));
-  }
-  int64_t *d_ro = static_cast<int64_t *>(d_rows) + m;
+  int64_t *d_ro = up.extra;
   double *d_mind = static_cast<double *>(d_out);
   int *d_near = reinterpret_cast<int *>(d_mind + m);
-  KS_TRY(seed_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_r, m, g, flags, first, u, d_ro, d_near, d_mind,
-                   pick_dist, potential, res, nullptr));
+  KS_TRY(seed_impl(ctx, up.sp, n, ncol, up.rows, m, g, flags, first, u, d_ro, d_near, d_mind, pick_dist, potential, res,
+                   nullptr));
   KS_HIP(hipMemcpyAsync(rows_out, d_ro, (size_t)g * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(near, d_near, (size_t)m * 4, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(mind, d_mind, (size_t)m * 8, hipMemcpyDeviceToHost, st));

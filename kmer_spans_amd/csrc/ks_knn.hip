@@ -11,13 +11,11 @@
 // lexicographic order of (acc, position), a total order: the result does not
 // depend on the tile shape, the grid or the split of the candidates.
 //
-// Normalise: k_knn_normalise, a wave per selected row, as k_km_normalise: the
-//            index is checked, the row summed in uint64 and p = cnt / T written
-//            to a ROW-MAJOR panel [rows][ncol] (the select kernel stages 16
-//            consecutive columns of a row, a 128-byte segment, for both sides,
-//            as k_km_assign does).  Bad indices and empty rows are recorded
-//            with integer atomicMax (the first position wins) and one 32-byte
-//            read-back ends the call before any output is written.
+// Normalise: the shared row-major profile panel (ks_panel.hip), one per side
+//            (the select kernel stages 16 consecutive columns of a row, a
+//            128-byte segment, for both sides, as k_km_assign does).  One
+//            32-byte read-back of both sides' words ends the call before any
+//            output is written.
 // Select:    k_knn_select: a block of 256 threads keeps 64 query rows and
 //            walks candidate tiles of 64, a thread a 4 x 4 register block of
 //            accumulators as in k_dist_tile / k_km_assign; chunks of 16 columns
@@ -48,7 +46,7 @@
 #include <cstring>
 #include <limits>
 
-#include "ks_internal.h"
+#include "ks_panel.h"
 
 namespace ks {
 namespace {
@@ -68,31 +66,6 @@ struct KnnState {
   // cnt - position of the first: bad query index / bad candidate index / empty query row / empty candidate row
   unsigned long long bad[4];
 };
-
-__global__ void __launch_bounds__(256) k_knn_normalise(const uint32_t *__restrict__ sp, int64_t n, int ncol,
-                                                       const int64_t *__restrict__ rows, int64_t cnt,
-                                                       double *__restrict__ panel, KnnState *__restrict__ state,
-                                                       int side) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wv;
-  if (s >= cnt) return;  // wave-uniform
-  const int64_t r = rows ? rows[s] : s;
-  if (r < 0 || r >= n) {
-    if (lane == 0) atomicMax(&state->bad[side], (unsigned long long)(cnt - s));
-    return;
-  }
-  const uint32_t *row = sp + (size_t)r * ncol;
-  unsigned long long t = 0;
-  for (int c = lane; c < ncol; c += 64) t += row[c];
-  for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d);
-  if (t == 0) {
-    if (lane == 0) atomicMax(&state->bad[2 + side], (unsigned long long)(cnt - s));
-    return;
-  }
-  const double tot = (double)t;  // below 2^44: exact
-  double *dst = panel + (size_t)s * ncol;
-  for (int c = lane; c < ncol; c += 64) dst[c] = (double)row[c] / tot;
-}
 
 __device__ __forceinline__ bool knn_before(double v, int p, double w, int q) { return v < w || (v == w && p < q); }
 
@@ -254,13 +227,6 @@ __global__ void __launch_bounds__(256) k_knn_merge(const double *__restrict__ pv
   dist[(size_t)i * k + lane] = take_root ? sqrt(lv) : lv;
 }
 
-struct DevFree {  // the work memory goes back before the call returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // The work memory of a call, one allocation: the panel, then the rest.
 struct KnnWork {
   double *pa = nullptr, *pb = nullptr, *pval = nullptr;
@@ -269,45 +235,35 @@ struct KnnWork {
   size_t panel_bytes = 0, bytes = 0;
   int nsplit = 1, tps = 1;
 
-  static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
   // base null: only the sizes.  nb 0: the self form, the candidates are the query panel.
   void lay(char *base, int64_t na, int64_t nb, int ncol, int k) {
-    size_t o = 0;
-    auto take = [&](size_t b) {
-      char *p = base ? base + o : nullptr;
-      o += up(b);
-      return p;
-    };
-    pa = reinterpret_cast<double *>(take((size_t)na * ncol * 8));
-    pb = nb ? reinterpret_cast<double *>(take((size_t)nb * ncol * 8)) : pa;
-    panel_bytes = o;
-    state = reinterpret_cast<KnnState *>(take(sizeof(KnnState)));
+    Arena a{base};
+    pa = a.take<double>((size_t)na * ncol);
+    pb = nb ? a.take<double>((size_t)nb * ncol) : pa;
+    panel_bytes = a.off;
+    state = a.take<KnnState>(1);
     if (nsplit > 1) {
-      pval = reinterpret_cast<double *>(take((size_t)nsplit * na * k * 8));
-      ppos = reinterpret_cast<int *>(take((size_t)nsplit * na * k * 4));
+      pval = a.take<double>((size_t)nsplit * na * k);
+      ppos = a.take<int>((size_t)nsplit * na * k);
     }
-    bytes = o;
+    bytes = a.off;
   }
 };
 
 ks_status check_knn_args(const void *spectra, int64_t n, int32_t ncol, const void *rows, int64_t na,
                          const void *rows_b, int64_t nb, int32_t k, int32_t flags, const void *index,
                          const void *dist) {
-  if (na < 1)
-    return fail(KS_ERR_ARG, "a nearest-neighbour call needs at least 1 query row (na = %lld)", (long long)na);
-  if (rows_b && nb < 1)
-    return fail(KS_ERR_ARG, "a nearest-neighbour call needs at least 1 candidate row (nb = %lld)", (long long)nb);
-  if (na > 0x7ffffffeLL || (rows_b && nb > 0x7ffffffeLL))
-    return fail(KS_ERR_ARG, "too many selected rows for one call");
-  if (ncol < 1 || ncol > KS_DIST_MAX_NCOL) return fail(KS_ERR_ARG, "ncol must be between 1 and %d", KS_DIST_MAX_NCOL);
+  KS_TRY(panel_check_count(na, 1, "a nearest-neighbour call", "query row", "na"));
+  if (rows_b) KS_TRY(panel_check_count(nb, 1, "a nearest-neighbour call", "candidate row", "nb"));
+  KS_TRY(panel_check_most(na, 0x7ffffffeLL));
+  if (rows_b) KS_TRY(panel_check_most(nb, 0x7ffffffeLL));
+  KS_TRY(panel_check_ncol(ncol, KS_DIST_MAX_NCOL));
   if (k < 1 || k > KS_KNN_MAX_K)
     return fail(KS_ERR_ARG, "k must be between 1 and %d (k = %d)", KS_KNN_MAX_K, (int)k);
   if (flags & ~KS_DIST_SQUARED)
     return fail(KS_ERR_ARG, "unknown flags 0x%x for a nearest-neighbour call", (unsigned)flags);
-  if (n < 0) return fail(KS_ERR_ARG, "the number of rows must not be negative");
-  if (!rows && na > n)
-    return fail(KS_ERR_ARG, "rows is NULL (rows 0 .. na - 1) but na = %lld exceeds n = %lld", (long long)na,
-                (long long)n);
+  KS_TRY(panel_check_n(n));
+  KS_TRY(panel_check_null_rows(rows, na, n, "rows", "na"));
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
   if (!index || !dist) return fail(KS_ERR_ARG, "null output");
   return KS_OK;
@@ -318,28 +274,6 @@ ks_status check_knn_k(bool self, int64_t na, int64_t nb, int k) {
   if (k > cand)
     return fail(KS_ERR_ARG, "k exceeds the number of candidate rows (k = %d, %lld candidate%s)", k, (long long)cand,
                 cand == 1 ? "" : "s");
-  return KS_OK;
-}
-
-const char *const kBadText[4] = {"row index %lld out of range", "row index %lld of the second selection out of range",
-                                 "row %lld has no counts", "row %lld of the second selection has no counts"};
-
-// Indices and row sums of the host selections, in the order the device check reports them.
-ks_status check_knn_rows_host(const uint32_t *spectra, int64_t n, int ncol, const int64_t *rows, int64_t na,
-                              const int64_t *rows_b, int64_t nb) {
-  const int64_t *sel[2] = {rows, rows_b};
-  const int64_t cnt[2] = {na, rows_b ? nb : 0};
-  for (int side = 0; side < 2; ++side)
-    if (sel[side])
-      for (int64_t s = 0; s < cnt[side]; ++s)
-        if (sel[side][s] < 0 || sel[side][s] >= n) return fail(KS_ERR_ARG, kBadText[side], (long long)s);
-  for (int side = 0; side < 2; ++side)
-    for (int64_t s = 0; s < cnt[side]; ++s) {
-      const uint32_t *row = spectra + (size_t)(sel[side] ? sel[side][s] : s) * ncol;
-      uint64_t t = 0;
-      for (int c = 0; c < ncol; ++c) t += row[c];
-      if (t == 0) return fail(KS_ERR_ARG, kBadText[2 + side], (long long)s);
-    }
   return KS_OK;
 }
 
@@ -382,27 +316,17 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   KS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_knn_select, 256, lds));
   split_plan(na, ncand, ncol, k, (int64_t)ctx->num_cus * std::max(per_cu, 1), &w.tps, &w.nsplit);
   w.lay(nullptr, na, self ? 0 : nb, ncol, k);
-  const hipError_t e = hipMalloc(&mem.p, w.bytes);
-  if (e != hipSuccess) {
-    mem.p = nullptr;
-    (void)hipGetLastError();
-    return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the profile panel failed: %s", w.bytes, hipGetErrorString(e));
-  }
+  KS_TRY(dev_alloc(&mem, w.bytes, "the profile panel"));
   w.lay(static_cast<char *>(mem.p), na, self ? 0 : nb, ncol, k);
 
   KS_HIP(hipEventRecord(ctx->ev[0], st));
   KS_HIP(hipMemsetAsync(w.state, 0, sizeof(KnnState), st));
-  hipLaunchKernelGGL(k_knn_normalise, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, st, sp, n, ncol, rows, na, w.pa,
-                     w.state, 0);
-  if (!self)
-    hipLaunchKernelGGL(k_knn_normalise, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, sp, n, ncol, rows_b, nb,
-                       w.pb, w.state, 1);
-  KS_HIP(hipGetLastError());
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, na, w.pa, nullptr, &w.state->bad[0], &w.state->bad[2]));
+  if (!self) KS_TRY(panel_normalise(ctx, sp, n, ncol, rows_b, nb, w.pb, nullptr, &w.state->bad[1], &w.state->bad[3]));
   unsigned long long hbad[4] = {0, 0, 0, 0};
   KS_HIP(hipMemcpyAsync(hbad, w.state->bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
-  for (int q = 0; q < 4; ++q)
-    if (hbad[q]) return fail(KS_ERR_ARG, kBadText[q], (long long)(((q & 1) ? nb : na) - (int64_t)hbad[q]));
+  KS_TRY(panel_report(hbad, 2, na, nb));
   KS_TRY(check_knn_k(self, na, nb, k));
   // from here on the outputs are written
   KS_HIP(hipEventRecord(ctx->ev[1], st));
@@ -420,15 +344,11 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   KS_HIP(hipEventRecord(ctx->ev[3], st));
   KS_HIP(hipStreamSynchronize(st));  // the work memory is freed on return
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[3]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-    stats->ms_select = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_merge = w.nsplit > 1 ? ms : 0.0;
+    KS_TRY(event_ms(ctx, 0, 3, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 1, 2, &stats->ms_select));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_merge));
+    if (w.nsplit == 1) stats->ms_merge = 0.0;
     stats->n_splits = w.nsplit;
     stats->tiles_per_split = w.tps;
     stats->panel_bytes = (int64_t)w.panel_bytes;
@@ -457,32 +377,20 @@ extern "C" ks_status ks_spectra_knn(ks_ctx *ctx, const uint32_t *spectra, int64_
                                     int64_t na, const int64_t *rows_b, int64_t nb, int32_t k, int32_t flags,
                                     int64_t *index, double *dist) {
   KS_TRY(check_knn_args(spectra, n, ncol, rows, na, rows_b, nb, k, flags, index, dist));
-  KS_TRY(check_knn_rows_host(spectra, n, ncol, rows, na, rows_b, nb));
+  KS_TRY(panel_check_rows_host(spectra, n, ncol, rows, na, rows_b, nb));
   KS_TRY(check_knn_k(rows_b == nullptr, na, nb, k));
   KS_TRY(default_ctx(&ctx));
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
-  const int64_t nbb = rows_b ? nb : 0;
+  void *d_out = nullptr;
   const size_t out_elems = (size_t)na * k;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(na + nbb + 1) * 8, &d_rows));
   KS_TRY(ensure(ctx, SLOT_REG_TMP, out_elems * 16, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, spectra, n, ncol, rows, na, rows_b, rows_b ? nb : 0, 0, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, spectra, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_r = nullptr, *d_rb = nullptr;
-  if (rows) {
-    d_r = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_r, rows, (size_t)na * 8, hipMemcpyHostToDevice, st));
-  }
-  if (rows_b) {
-    d_rb = static_cast<int64_t *>(d_rows) + na;
-    KS_HIP(hipMemcpyAsync(d_rb, rows_b, (size_t)nb * 8, hipMemcpyHostToDevice, st));
-  }
   int64_t *d_idx = static_cast<int64_t *>(d_out);
   double *d_dist = reinterpret_cast<double *>(d_idx + out_elems);
-  KS_TRY(knn_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_r, na, d_rb, nb, k, flags, d_idx, d_dist,
-                  nullptr));
+  KS_TRY(knn_impl(ctx, up.sp, n, ncol, up.rows, na, up.rows_b, nb, k, flags, d_idx, d_dist, nullptr));
   KS_HIP(hipMemcpyAsync(index, d_idx, out_elems * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(dist, d_dist, out_elems * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));

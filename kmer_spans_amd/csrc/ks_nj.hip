@@ -343,13 +343,6 @@ __global__ void __launch_bounds__(kNjThreads) k_nj_root(const double *__restrict
   st.root_length[2] = 0.5 * ((dxz + dyz) - dxy);
 }
 
-struct DevFree {  // the call's allocations go back before it returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // ------------------------------------------------------------------- host
 
 ks_status check_nj_args(int64_t n, int32_t flags, const void *diss, const void *join, const void *length,
@@ -359,16 +352,6 @@ ks_status check_nj_args(int64_t n, int32_t flags, const void *diss, const void *
   if (flags & ~(KS_NJ_KEEP_INPUT | KS_NJ_NO_COMPACT)) return fail(KS_ERR_ARG, "unknown nj flags 0x%x", (unsigned)flags);
   if (!diss) return fail(KS_ERR_ARG, "null dissimilarities");
   if (!join || !length || !root || !root_length) return fail(KS_ERR_ARG, "null output");
-  return KS_OK;
-}
-
-ks_status dev_alloc(DevFree *f, size_t bytes, const char *what) {
-  const hipError_t e = hipMalloc(&f->p, bytes);
-  if (e != hipSuccess) {
-    f->p = nullptr;
-    (void)hipGetLastError();
-    return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for %s failed: %s", bytes, what, hipGetErrorString(e));
-  }
   return KS_OK;
 }
 
@@ -444,15 +427,10 @@ ks_status nj_impl(ks_ctx *ctx, double *diss, int64_t n, int flags, int32_t *join
   if (tail[0] == 1) return fail(KS_ERR_ARG, "no pair with a criterion below +inf was left to join: the row sums overflowed");
   if (tail[0]) return fail(KS_ERR_DEVICE, "neighbour joining did not end with three live rows");
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_check = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_init = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    stats->ms_join = ms;
+    KS_TRY(event_ms(ctx, 0, 4, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_check));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_init));
+    KS_TRY(event_ms(ctx, 3, 4, &stats->ms_join));
     stats->n = n;
     stats->n_compactions = n_compactions;
     stats->work_bytes = work;

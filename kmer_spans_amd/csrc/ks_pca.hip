@@ -13,11 +13,9 @@
 // depend on tile shape or grid and a host loop predicts them.  The eigen stage
 // uses sqrt and division and is fixed as an algorithm, not as bits.
 //
-// Normalise: k_pca_normalise, a wave per selected row: the index is checked, the
-//            row summed in uint64 and p = cnt / T written to the ROW-MAJOR panel
-//            [m][ncol].  A bad index or an empty row is recorded (atomicMax on
-//            integers: the first position wins) and one 16-byte read-back ends
-//            the call before any output is written.
+// Normalise: the shared row-major profile panel [m][ncol] (ks_panel.hip); one
+//            16-byte read-back of its two words ends the call before any output
+//            is written.
 // Centre:    k_pca_center: a block per 16 columns stages 128 rows at a time in
 //            LDS with all 256 threads (the loads are what is slow), then 16
 //            threads run the 16 column chains over the staged rows: the chains
@@ -48,7 +46,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "ks_internal.h"
+#include "ks_panel.h"
 // after hip_runtime.h (ks_internal.h): the header's functions are __host__ __device__ here
 #include "ks_dist_index.h"
 
@@ -82,30 +80,6 @@ __host__ __device__ inline void pca_slot_pair(int P, int round, int i, int *p, i
   }
   *p = a < b ? a : b;
   *q = a < b ? b : a;
-}
-
-__global__ void __launch_bounds__(256) k_pca_normalise(const uint32_t *__restrict__ sp, int64_t n, int ncol,
-                                                       const int64_t *__restrict__ rows, int64_t cnt,
-                                                       double *__restrict__ panel, PcaState *__restrict__ state) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wv;
-  if (s >= cnt) return;  // wave-uniform
-  const int64_t r = rows ? rows[s] : s;
-  if (r < 0 || r >= n) {
-    if (lane == 0) atomicMax(&state->bad[0], (unsigned long long)(cnt - s));
-    return;
-  }
-  const uint32_t *row = sp + (size_t)r * ncol;
-  unsigned long long t = 0;
-  for (int c = lane; c < ncol; c += 64) t += row[c];
-  for (int d = 32; d > 0; d >>= 1) t += __shfl_xor(t, d);
-  if (t == 0) {
-    if (lane == 0) atomicMax(&state->bad[1], (unsigned long long)(cnt - s));
-    return;
-  }
-  const double tot = (double)t;  // below 2^44: exact
-  double *dst = panel + (size_t)s * ncol;
-  for (int c = lane; c < ncol; c += 64) dst[c] = (double)row[c] / tot;
 }
 
 __global__ void __launch_bounds__(256) k_pca_center(const double *__restrict__ panel, int64_t m, int ncol,
@@ -392,23 +366,14 @@ __global__ void __launch_bounds__(256) k_pca_project(const double *__restrict__ 
   }
 }
 
-struct DevFree {  // the work memory goes back before the call returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 ks_status check_pca_args(int64_t n, int32_t ncol, const void *rows, int64_t m, int32_t flags, int32_t ncomp) {
-  if (m < 2) return fail(KS_ERR_ARG, "a principal component analysis needs at least 2 rows (m = %lld)", (long long)m);
-  if (m > 0x7fffffffLL) return fail(KS_ERR_ARG, "too many selected rows for one call");
-  if (ncol < 1 || ncol > KS_PCA_MAX_NCOL) return fail(KS_ERR_ARG, "ncol must be between 1 and %d", KS_PCA_MAX_NCOL);
+  KS_TRY(panel_check_count(m, 2, "a principal component analysis", "row", "m"));
+  KS_TRY(panel_check_most(m, 0x7fffffffLL));
+  KS_TRY(panel_check_ncol(ncol, KS_PCA_MAX_NCOL));
   if (ncomp < 1 || ncomp > ncol) return fail(KS_ERR_ARG, "ncomp must be between 1 and ncol = %d", (int)ncol);
   if (flags & ~KS_PCA_NO_CENTER) return fail(KS_ERR_ARG, "unknown pca flags 0x%x", (unsigned)flags);
-  if (n < 0) return fail(KS_ERR_ARG, "the number of rows must not be negative");
-  if (!rows && m > n) return fail(KS_ERR_ARG, "rows is NULL (rows 0 .. m - 1) but m = %lld exceeds n = %lld",
-                                  (long long)m, (long long)n);
-  return KS_OK;
+  KS_TRY(panel_check_n(n));
+  return panel_check_null_rows(rows, m, n, "rows", "m");
 }
 
 inline size_t pad16(size_t doubles) { return (doubles + 15) & ~(size_t)15; }
@@ -421,14 +386,7 @@ ks_status pca_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   const size_t panel_d = pad16((size_t)m * ncol), mat_d = pad16((size_t)P * P);
   const size_t work_bytes = (panel_d + 3 * mat_d) * 8 + sizeof(PcaState);
   DevFree mem;
-  {
-    hipError_t e = hipMalloc(&mem.p, work_bytes);
-    if (e != hipSuccess) {
-      mem.p = nullptr;
-      (void)hipGetLastError();
-      return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the profile panel failed: %s", work_bytes, hipGetErrorString(e));
-    }
-  }
+  KS_TRY(dev_alloc(&mem, work_bytes, "the profile panel"));
   double *panel = static_cast<double *>(mem.p);
   double *a[2] = {panel + panel_d, panel + panel_d + mat_d};
   double *v = panel + panel_d + 2 * mat_d;
@@ -437,14 +395,11 @@ ks_status pca_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   // profiles; every index and every row sum is checked before any output is written
   KS_HIP(hipEventRecord(ctx->ev[0], st));
   KS_HIP(hipMemsetAsync(state, 0, sizeof(PcaState), st));
-  hipLaunchKernelGGL(k_pca_normalise, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, sp, n, ncol, rows, m, panel,
-                     state);
-  KS_HIP(hipGetLastError());
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, panel, nullptr, &state->bad[0], &state->bad[1]));
   unsigned long long hbad[2] = {0, 0};
   KS_HIP(hipMemcpyAsync(hbad, state->bad, 16, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
-  if (hbad[0]) return fail(KS_ERR_ARG, "row index %lld out of range", (long long)(m - (int64_t)hbad[0]));
-  if (hbad[1]) return fail(KS_ERR_ARG, "row %lld has no counts", (long long)(m - (int64_t)hbad[1]));
+  KS_TRY(panel_report(hbad, 1, m, 0));
 
   if (flags & KS_PCA_NO_CENTER) {
     KS_HIP(hipMemsetAsync(center, 0, (size_t)ncol * 8, st));
@@ -515,17 +470,11 @@ ks_status pca_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   KS_HIP(hipEventRecord(ctx->ev[4], st));
   KS_HIP(hipStreamSynchronize(st));  // the work memory is freed on return
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-    stats->ms_gram = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_eigen = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    stats->ms_project = ms;
+    KS_TRY(event_ms(ctx, 0, 4, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 1, 2, &stats->ms_gram));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_eigen));
+    KS_TRY(event_ms(ctx, 3, 4, &stats->ms_project));
     stats->n_sweeps = n_sweeps;
     stats->n_rotations = n_rot;
     stats->panel_bytes = (int64_t)work_bytes;
@@ -558,35 +507,21 @@ extern "C" ks_status ks_spectra_pca(ks_ctx *ctx, const uint32_t *spectra, int64_
   KS_TRY(check_pca_args(n, ncol, rows, m, flags, ncomp));
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
   if (!center || !sdev || !rotation) return fail(KS_ERR_ARG, "null output");
-  if (rows)
-    for (int64_t s = 0; s < m; ++s)
-      if (rows[s] < 0 || rows[s] >= n) return fail(KS_ERR_ARG, "row index %lld out of range", (long long)s);
-  for (int64_t s = 0; s < m; ++s) {
-    const uint32_t *row = spectra + (size_t)(rows ? rows[s] : s) * ncol;
-    uint64_t t = 0;
-    for (int c = 0; c < ncol; ++c) t += row[c];
-    if (t == 0) return fail(KS_ERR_ARG, "row %lld has no counts", (long long)s);
-  }
+  KS_TRY(panel_check_rows_host(spectra, n, ncol, rows, m, nullptr, 0));
   KS_TRY(default_ctx(&ctx));
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
   // outputs in one block: center | sdev | rotation | x | G
   const size_t o_sdev = (size_t)ncol, o_rot = 2 * (size_t)ncol, o_x = o_rot + (size_t)ncol * ncomp;
   const size_t o_g = o_x + (x ? (size_t)m * ncomp : 0), o_end = o_g + (gram ? (size_t)ncol * ncol : 0);
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(m + 1) * 8, &d_rows));
+  void *d_out = nullptr;
   KS_TRY(ensure(ctx, SLOT_REG_TMP, o_end * 8, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, spectra, n, ncol, rows, m, nullptr, 0, 0, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, spectra, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_r = nullptr;
-  if (rows) {
-    d_r = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_r, rows, (size_t)m * 8, hipMemcpyHostToDevice, st));
-  }
   double *o = static_cast<double *>(d_out);
-  KS_TRY(pca_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_r, m, flags, ncomp, o, o + o_sdev, o + o_rot,
-                  x ? o + o_x : nullptr, gram ? o + o_g : nullptr, nullptr));
+  KS_TRY(pca_impl(ctx, up.sp, n, ncol, up.rows, m, flags, ncomp, o, o + o_sdev, o + o_rot, x ? o + o_x : nullptr,
+                  gram ? o + o_g : nullptr, nullptr));
   KS_HIP(hipMemcpyAsync(center, o, (size_t)ncol * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(sdev, o + o_sdev, (size_t)ncol * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipMemcpyAsync(rotation, o + o_rot, (size_t)ncol * ncomp * 8, hipMemcpyDeviceToHost, st));

@@ -154,13 +154,6 @@ __global__ void __launch_bounds__(256) k_sil_widths(int n, SilState st) {
   st.width[i] = w;
 }
 
-struct DevFree {  // the call's allocations go back before it returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // ------------------------------------------------------------------- host
 
 // Everything but the entries of diss, on the host.  size: [ngroups], filled.
@@ -272,15 +265,10 @@ ks_status sil_impl(ks_ctx *ctx, const double *diss, int64_t n, const int32_t *gr
     avg_width[c] = acc / (double)size[c];
   }
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_check = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
-    stats->ms_sums = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    stats->ms_widths = ms;
+    KS_TRY(event_ms(ctx, 0, 4, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_check));
+    KS_TRY(event_ms(ctx, 2, 3, &stats->ms_sums));
+    KS_TRY(event_ms(ctx, 3, 4, &stats->ms_widths));
     stats->n = n;
     stats->ngroups = g;
     stats->n_chunks = nchunks;
@@ -323,15 +311,7 @@ extern "C" ks_status ks_silhouette(ks_ctx *ctx, const double *diss, int64_t n, c
   void *d = nullptr;
   DevFree sums_dev;
   KS_TRY(ensure(ctx, SLOT_REG_TMP, (size_t)total * 8, &d));
-  if (sums) {
-    const size_t bytes = (size_t)n * ngroups * 8;
-    const hipError_t e = hipMalloc(&sums_dev.p, bytes);
-    if (e != hipSuccess) {
-      sums_dev.p = nullptr;
-      (void)hipGetLastError();
-      return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the group sums failed: %s", bytes, hipGetErrorString(e));
-    }
-  }
+  if (sums) KS_TRY(dev_alloc(&sums_dev, (size_t)n * ngroups * 8, "the group sums"));
   KS_HIP(hipMemcpyAsync(d, diss, (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
   KS_TRY(sil_impl(ctx, static_cast<const double *>(d), n, group, ngroups, width, a, b, neighbor, size, medoid,
                   diameter, avg_width, avg_width_all, static_cast<double *>(sums_dev.p), nullptr));

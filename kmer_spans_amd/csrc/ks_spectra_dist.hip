@@ -37,7 +37,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "ks_internal.h"
+#include "ks_panel.h"
 // after hip_runtime.h (ks_internal.h): the header's functions are __host__ __device__ here
 #include "ks_dist_index.h"
 
@@ -217,13 +217,6 @@ __global__ void __launch_bounds__(kNaive *kNaive) k_dist_naive(const double *__r
 }
 #endif
 
-struct DevFree {  // the panel goes back before the call returns, whichever way it ends
-  void *p = nullptr;
-  ~DevFree() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // Blocks of the distance launch (a linear grid), -1 when one launch cannot hold them.
 int64_t dist_grid(bool cross, int64_t ma, int64_t mb, int64_t *tiles_b) {
   const int64_t ta = (ma + kEdge - 1) / kEdge, tb = cross ? (mb + kEdge - 1) / kEdge : ta;
@@ -234,20 +227,13 @@ int64_t dist_grid(bool cross, int64_t ma, int64_t mb, int64_t *tiles_b) {
 }
 
 ks_status check_dist_args(bool cross, int64_t n, int32_t ncol, int64_t ma, int64_t mb, int32_t flags) {
-  if (ncol < 1 || ncol > KS_DIST_MAX_NCOL) return fail(KS_ERR_ARG, "ncol must be between 1 and %d", KS_DIST_MAX_NCOL);
+  KS_TRY(panel_check_ncol(ncol, KS_DIST_MAX_NCOL));
   if (flags & ~KS_DIST_SQUARED) return fail(KS_ERR_ARG, "unknown distance flags 0x%x", (unsigned)flags);
-  if (n < 0) return fail(KS_ERR_ARG, "the number of rows must not be negative");
+  KS_TRY(panel_check_n(n));
   if (ma < 0 || mb < 0) return fail(KS_ERR_ARG, "the number of selected rows must not be negative");
   int64_t tb;
   if (dist_grid(cross, ma, mb, &tb) < 0)  // beyond 2^31 - 1 tiles: tens of terabytes of output
     return fail(KS_ERR_ARG, "too many selected rows for one call: walk the list in blocks");
-  return KS_OK;
-}
-
-// A NULL selection of cnt rows is rows 0 .. cnt - 1.
-ks_status check_null_selection(const void *rows, int64_t cnt, int64_t n, const char *what) {
-  if (!rows && cnt > n) return fail(KS_ERR_ARG, "%s is NULL (rows 0 .. m - 1) but m = %lld exceeds n = %lld", what,
-                                    (long long)cnt, (long long)n);
   return KS_OK;
 }
 
@@ -270,12 +256,10 @@ ks_status dist_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
       hipLaunchKernelGGL(k_dist_check, dim3((unsigned)((mb + 255) / 256)), dim3(256), 0, st, rows_b, mb, n, bad + 1);
       KS_HIP(hipGetLastError());
     }
-    unsigned long long hbad[2] = {0, 0};
+    unsigned long long hbad[4] = {0, 0, 0, 0};  // both selections' index words; no row is refused for its sum here
     KS_HIP(hipMemcpyAsync(hbad, bad, 16, hipMemcpyDeviceToHost, st));
     KS_HIP(hipStreamSynchronize(st));
-    if (hbad[0]) return fail(KS_ERR_ARG, "row index %lld out of range", (long long)(ma - (int64_t)hbad[0]));
-    if (hbad[1]) return fail(KS_ERR_ARG, "row index %lld of the second selection out of range",
-                             (long long)(mb - (int64_t)hbad[1]));
+    KS_TRY(panel_report(hbad, 2, ma, mb));
   }
   const int64_t pairs = cross ? ma * mb : dist_pair_count(ma);
   if (pairs == 0) return KS_OK;
@@ -283,14 +267,7 @@ ks_status dist_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   const int64_t ld = ma + mb;
   DevFree panel_mem;
   const size_t panel_bytes = (size_t)ld * ncol * 8;
-  {
-    hipError_t e = hipMalloc(&panel_mem.p, panel_bytes);
-    if (e != hipSuccess) {
-      panel_mem.p = nullptr;
-      (void)hipGetLastError();
-      return fail(KS_ERR_NOMEM, "hipMalloc(%zu) for the profile panel failed: %s", panel_bytes, hipGetErrorString(e));
-    }
-  }
+  KS_TRY(dev_alloc(&panel_mem, panel_bytes, "the profile panel"));
   double *panel = static_cast<double *>(panel_mem.p);
 
   KS_HIP(hipEventRecord(ctx->ev[0], st));
@@ -325,24 +302,13 @@ ks_status dist_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   KS_HIP(hipEventRecord(ctx->ev[2], st));
   KS_HIP(hipStreamSynchronize(st));  // the panel is freed on return
   if (stats) {
-    float ms = 0;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[2]));
-    stats->ms_total = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    stats->ms_normalise = ms;
-    KS_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-    stats->ms_distance = ms;
+    KS_TRY(event_ms(ctx, 0, 2, &stats->ms_total));
+    KS_TRY(event_ms(ctx, 0, 1, &stats->ms_normalise));
+    KS_TRY(event_ms(ctx, 1, 2, &stats->ms_distance));
     stats->n_pairs = pairs;
     stats->bytes_written = pairs * 8;
     stats->panel_bytes = (int64_t)panel_bytes;
   }
-  return KS_OK;
-}
-
-ks_status check_rows_host(const int64_t *rows, int64_t cnt, int64_t n, const char *fmt) {
-  if (!rows) return KS_OK;
-  for (int64_t s = 0; s < cnt; ++s)
-    if (rows[s] < 0 || rows[s] >= n) return fail(KS_ERR_ARG, fmt, (long long)s);
   return KS_OK;
 }
 
@@ -353,23 +319,13 @@ ks_status dist_host(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   KS_ENTER(ctx);
   const HostEnd host_end{ctx};  // (ks_set_host_cache)
   const int64_t pairs = cross ? ma * mb : dist_pair_count(ma);
-  void *d_sp = nullptr, *d_rows = nullptr, *d_out = nullptr;
-  KS_TRY(ensure(ctx, SLOT_COUNTS, (size_t)n * ncol * 4, &d_sp));
-  KS_TRY(ensure(ctx, SLOT_REGIONS, (size_t)(ma + mb + 1) * 8, &d_rows));
+  void *d_out = nullptr;
   KS_TRY(ensure(ctx, SLOT_REG_TMP, (size_t)pairs * 8, &d_out));
+  SpectraUpload up;
+  KS_TRY(upload_spectra(ctx, sp, n, ncol, rows_a, ma, cross ? rows_b : nullptr, mb, 0, &up));
   hipStream_t st = ctx->stream;
-  KS_HIP(hipMemcpyAsync(d_sp, sp, (size_t)n * ncol * 4, hipMemcpyHostToDevice, st));
-  int64_t *d_ra = nullptr, *d_rb = nullptr;
-  if (rows_a) {
-    d_ra = static_cast<int64_t *>(d_rows);
-    KS_HIP(hipMemcpyAsync(d_ra, rows_a, (size_t)ma * 8, hipMemcpyHostToDevice, st));
-  }
-  if (cross && rows_b) {
-    d_rb = static_cast<int64_t *>(d_rows) + ma;
-    KS_HIP(hipMemcpyAsync(d_rb, rows_b, (size_t)mb * 8, hipMemcpyHostToDevice, st));
-  }
-  KS_TRY(dist_impl(ctx, static_cast<const uint32_t *>(d_sp), n, ncol, d_ra, ma, d_rb, mb, cross, flags,
-                   static_cast<double *>(d_out), nullptr));
+  KS_TRY(dist_impl(ctx, up.sp, n, ncol, up.rows, ma, up.rows_b, mb, cross, flags, static_cast<double *>(d_out),
+                   nullptr));
   KS_HIP(hipMemcpyAsync(out, d_out, (size_t)pairs * 8, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
   return KS_OK;
@@ -386,7 +342,7 @@ extern "C" ks_status ks_spectra_dist_dev(ks_ctx *ctx, const uint32_t *spectra_de
   if (stats) memset(stats, 0, sizeof(*stats));
   KS_TRY(check_dist_args(false, n, ncol, m, 0, flags));
   if (m == 0) return KS_OK;
-  KS_TRY(check_null_selection(rows_dev, m, n, "rows_dev"));
+  KS_TRY(panel_check_null_rows(rows_dev, m, n, "rows_dev", "m"));
   if (!spectra_dev) return fail(KS_ERR_ARG, "null spectra");
   if (m > 1 && !out_dev) return fail(KS_ERR_ARG, "null output");
   KS_TRY(default_ctx(&ctx));
@@ -400,8 +356,8 @@ extern "C" ks_status ks_spectra_cross_dist_dev(ks_ctx *ctx, const uint32_t *spec
   if (stats) memset(stats, 0, sizeof(*stats));
   KS_TRY(check_dist_args(true, n, ncol, na, nb, flags));
   if (na == 0 && nb == 0) return KS_OK;
-  KS_TRY(check_null_selection(rows_a_dev, na, n, "rows_a_dev"));
-  KS_TRY(check_null_selection(rows_b_dev, nb, n, "rows_b_dev"));
+  KS_TRY(panel_check_null_rows(rows_a_dev, na, n, "rows_a_dev", "m"));
+  KS_TRY(panel_check_null_rows(rows_b_dev, nb, n, "rows_b_dev", "m"));
   if (!spectra_dev) return fail(KS_ERR_ARG, "null spectra");
   if (na > 0 && nb > 0 && !out_dev) return fail(KS_ERR_ARG, "null output");
   KS_TRY(default_ctx(&ctx));
@@ -413,9 +369,9 @@ extern "C" ks_status ks_spectra_dist(ks_ctx *ctx, const uint32_t *spectra, int64
                                      const int64_t *rows, int64_t m, int32_t flags, double *out) {
   KS_TRY(check_dist_args(false, n, ncol, m, 0, flags));
   if (m == 0) return KS_OK;
-  KS_TRY(check_null_selection(rows, m, n, "rows"));
+  KS_TRY(panel_check_null_rows(rows, m, n, "rows", "m"));
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
-  KS_TRY(check_rows_host(rows, m, n, "row index %lld out of range"));
+  KS_TRY(panel_check_index_host(rows, m, n, 0));
   if (m == 1) return KS_OK;  // no pair: nothing to write
   if (!out) return fail(KS_ERR_ARG, "null output");
   return dist_host(ctx, spectra, n, ncol, rows, m, nullptr, 0, false, flags, out);
@@ -426,11 +382,11 @@ extern "C" ks_status ks_spectra_cross_dist(ks_ctx *ctx, const uint32_t *spectra,
                                            int32_t flags, double *out) {
   KS_TRY(check_dist_args(true, n, ncol, na, nb, flags));
   if (na == 0 && nb == 0) return KS_OK;
-  KS_TRY(check_null_selection(rows_a, na, n, "rows_a"));
-  KS_TRY(check_null_selection(rows_b, nb, n, "rows_b"));
+  KS_TRY(panel_check_null_rows(rows_a, na, n, "rows_a", "m"));
+  KS_TRY(panel_check_null_rows(rows_b, nb, n, "rows_b", "m"));
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
-  KS_TRY(check_rows_host(rows_a, na, n, "row index %lld out of range"));
-  KS_TRY(check_rows_host(rows_b, nb, n, "row index %lld of the second selection out of range"));
+  KS_TRY(panel_check_index_host(rows_a, na, n, 0));
+  KS_TRY(panel_check_index_host(rows_b, nb, n, 1));
   if (na == 0 || nb == 0) return KS_OK;
   if (!out) return fail(KS_ERR_ARG, "null output");
   return dist_host(ctx, spectra, n, ncol, rows_a, na, rows_b, nb, true, flags, out);
