@@ -445,7 +445,23 @@ ks_status ks_tr_lr_dev(ks_ctx *ctx, const ks_dev_seqs *seqs, int32_t k, const ks
  * also counts as a hint_reuses).  A failed check reruns the call on the hint
  * path (entry_fallbacks).  The thresholds and the visit histogram are not part
  * of the key: every index is scored and every excursion emitted under the
- * call's own.  KS_NO_EXACT_ENTRY=1 (read per call) switches it off. */
+ * call's own.  KS_NO_EXACT_ENTRY=1 (read per call) switches it off.
+ *
+ * The first scan from exact entries (the second scan of a genome with a
+ * table) also writes the uint16 value code of every scan index into a slot of
+ * its own, 2 B per scan index of the genome (about 6.2 GB at 3.1 Gbp); the
+ * scans after it stream those codes instead of reading the table's lines
+ * (ks_seq_index_codes_info: code_builds, code_reuses).  The codes depend on
+ * the bytes, k, the scan kind and the table(s) only, the key of the exact
+ * entries, and go wherever those go.  Every exact entry is still verified, and
+ * one code in 64 chunks is compared with the table; a failure reruns the call
+ * on the hint path (code_fallbacks) and the codes are written again.  That
+ * check is a tripwire for contract violations, as the check against the bytes
+ * is, not a proof.  Only compressed wide-line and uint16-line tables whose
+ * distinct values fit the LDS copy keep codes; a new threshold inside the
+ * table (thr) or another k is another table and starts over.  Without the
+ * memory for the slot the scan goes on without it (code_alloc_failures).
+ * KS_NO_KEPT_CODES=1 (read per call) switches the path and the slot off. */
 typedef struct ks_seq_index ks_seq_index;
 ks_status ks_seq_index_create(const ks_dev_seqs *seqs, ks_seq_index **out);
 void ks_seq_index_destroy(ks_seq_index *ix);
@@ -465,6 +481,19 @@ ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_info *out);
  * entries and verified them (entry_reuses), and calls whose verification
  * failed and that were rerun on the hint path (entry_fallbacks). */
 ks_status ks_seq_index_entry_info(const ks_seq_index *ix, int64_t *entry_reuses, int64_t *entry_fallbacks);
+/* The kept codes: scans that wrote them, scans that read them, reading calls
+ * rerun on the hint path, calls that went without the slot for want of memory. */
+ks_status ks_seq_index_codes_info(const ks_seq_index *ix, int64_t *code_builds, int64_t *code_reuses,
+                                  int64_t *code_fallbacks, int64_t *code_alloc_failures);
+/* Diagnostics for tests.  ks_kept_codes_layout: the bytes of the kept codes of
+ * nch chunks in steps of J scan indices and the halfword offset of scan index
+ * i of chunk c (host arithmetic).  ks_kept_codes_debug_read: the kept codes of
+ * chunks [c0, c0 + nchunks) of the context's last chunked scan in index order,
+ * 256 per chunk (indices past a chunk's length hold anything), and the step J;
+ * a synchronous copy, nothing is written to the device; KS_ERR_ARG when the
+ * context keeps no codes.  ctx NULL: the default context. */
+ks_status ks_kept_codes_layout(int32_t J, int64_t nch, int64_t c, int32_t i, int64_t *bytes, int64_t *halfword);
+ks_status ks_kept_codes_debug_read(ks_ctx *ctx, int64_t c0, int64_t nchunks, uint16_t *dst_host, int32_t *steps_J);
 ks_status ks_scan_dev_indexed(ks_ctx *ctx, const ks_dev_seqs *seqs, ks_seq_index *ix, int32_t k,
                               const ks_table *table, int32_t min_width, double min_score, int32_t *visits_dev,
                               ks_regions *out, ks_scan_stats *stats);

@@ -212,6 +212,7 @@ EXPORTS = [
     "ks_spectra_kmeans_seed", "ks_spectra_kmeans_seed_dev",
     "ks_spectra_knn", "ks_spectra_knn_dev",
     "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
+    "ks_seq_index_codes_info", "ks_kept_codes_layout", "ks_kept_codes_debug_read",
     "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
     "ks_scan_chunk_indices", "ks_scan_tile_chunks",
 ]

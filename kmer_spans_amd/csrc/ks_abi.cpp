@@ -40,6 +40,10 @@ ks_status fail(ks_status st, const char *fmt, ...) {
   return st;
 }
 
+// Blanks the thread's last-error string: for a failure a call recovered from
+// and does not report (it returns KS_OK).
+void clear_last_error() { g_err[0] = '\0'; }
+
 // The process that first touched HIP through this library.  HIP state does
 // not survive fork(): a child (R's mclapply, test.R:550-567) that inherits a
 // context must not use it -- a HIP call there can hang -- so every entry
@@ -220,6 +224,7 @@ ks_status ensure(ks_ctx *ctx, Slot s, size_t bytes, void **out) {
     // a sequence index's data does not survive a new buffer for one of its slots
     if (s == SLOT_PACKED || s == SLOT_RUNS || s == SLOT_LAYOUT) seq_cache_clear(ctx);
     if (s == SLOT_CHUNK_KEEP) chunk_keep_clear(ctx);  // (the kept chunk table and hint go with their buffer)
+    if (s == SLOT_CODE_KEEP) ctx->chunk_keep.codes_ok = false;  // (the kept codes alone with theirs)
     if (b.ptr) {
       // every stream of the context may still use the old buffer (the
       // piecewise count of a host entry runs on the side stream, pass 1's
@@ -422,6 +427,7 @@ static double idle_ms() {
 // and the context's ownership word) and ks_release_cache.
 static void free_workspace(ks_ctx *c) {
   seq_cache_clear(c);
+  c->code_keep_refused = 0;  // (memory goes back: the kept codes' slot may be asked for again)
   (void)hipSetDevice(c->device);
   bool any = false;
   for (auto &b : c->slots) any = any || b.ptr;
@@ -748,6 +754,17 @@ extern "C" ks_status ks_seq_index_info_get(const ks_seq_index *ix, ks_seq_index_
   out->chunk_reuses = ix->chunk_reuses;
   out->hint_reuses = ix->hint_reuses;
   out->predictor_builds = ix->predictor_builds;
+  return KS_OK;
+}
+
+extern "C" ks_status ks_seq_index_codes_info(const ks_seq_index *ix, int64_t *code_builds, int64_t *code_reuses,
+                                             int64_t *code_fallbacks, int64_t *code_alloc_failures) {
+  if (!ix || !code_builds || !code_reuses || !code_fallbacks || !code_alloc_failures)
+    return fail(KS_ERR_ARG, "null argument");
+  *code_builds = ix->code_builds;
+  *code_reuses = ix->code_reuses;
+  *code_fallbacks = ix->code_fallbacks;
+  *code_alloc_failures = ix->code_alloc_failures;
   return KS_OK;
 }
 

@@ -27,6 +27,7 @@ constexpr ks_status KS_INTERNAL_RETRY = static_cast<ks_status>(100);
 // ---------------------------------------------------------------- errors
 void set_error(const char *fmt, ...);
 ks_status fail(ks_status st, const char *fmt, ...);
+void clear_last_error();  // a failure the call recovered from is not its last error
 
 #define KS_HIP(call)                                                                  \
   do {                                                                                \
@@ -68,6 +69,7 @@ enum Slot : int {
   SLOT_STAGE_NIB,   // host entry staging: 4-bit base classes as sent over PCIe
   SLOT_RANKS,       // host low-comp entry: the weighted-rank vector (FP64 [4^k]) on its way out
   SLOT_CHUNK_KEEP,  // chunked scan: chunk table, tile map and entry hints, kept between scans (ChunkKeep)
+  SLOT_CODE_KEEP,   // chunked scan: the uint16 value code of every scan index, kept between scans (ChunkKeep::codes_ok)
   SLOT_COUNT
 };
 
@@ -157,6 +159,13 @@ struct ChunkKeep {
   // Keep::entry holds every chunk's exact entry under the hint's key: the call
   // that set the tag wrote (general path) or verified (exact-entry path) all of them
   bool entry_ok = false;
+  // SLOT_CODE_KEEP (buffer codes_base) holds the value code of every scan index
+  // under the same key, in steps of codes_J indices (ks_scan_chunked.hip,
+  // kc_slot): written by the first scan from exact entries, read by the later
+  // ones.  Goes with the tag, and alone where ensure regrows its slot.
+  bool codes_ok = false;
+  const void *codes_base = nullptr;
+  int codes_J = 0;
 };
 
 // Process-unique id of a score table (ks_table::id, never 0): a table
@@ -200,6 +209,7 @@ struct ks_ctx {
   bool vis_count_ext_used = false;
   ks::SeqCache seq_cache;  // (ks_runs.hip: find_runs / run_layout; cleared wherever the three slots go)
   ks::ChunkKeep chunk_keep;  // (ks_scan_chunked.hip; cleared with seq_cache and wherever its slot goes)
+  size_t code_keep_refused = 0;  // bytes of a SLOT_CODE_KEEP request the driver refused (0: none); cleared by free_workspace
 };
 
 // A sequence index (include/kmer_spans.h): a host record of which sequences
@@ -218,6 +228,9 @@ struct ks_seq_index {
   // pass 1 started from the kept exact entries and verified them (no P2-P4); a verification
   // failed and the call was rerun on the hint path (ks_seq_index_entry_info)
   int64_t entry_reuses = 0, entry_fallbacks = 0;
+  // the kept codes (ks_seq_index_codes_info): scans that wrote them, scans that read them,
+  // reading calls rerun on the hint path, calls that went without them for want of memory
+  int64_t code_builds = 0, code_reuses = 0, code_fallbacks = 0, code_alloc_failures = 0;
 };
 
 struct ks_table {

@@ -286,6 +286,59 @@ __device__ __forceinline__ void load_codes16(const uint16_t *__restrict__ codes,
   }
 }
 
+// The kept codes (SLOT_CODE_KEEP, ChunkKeep::codes_ok): the uint16 LUT index
+// of every scan index, in the steps of J indices the line pass that wrote them
+// walks (k_pass1w / k_pass1l, kStore).  A step's J codes are one record of
+// W = (J + 1) / 2 dwords, code t in halfword t, and the records lie
+// [tile = c / 64][step][lane = c % 64]: a wave writes (and k_pass1c reads) one
+// contiguous run of 64 W dwords per step.  J = 6: 43 steps x 12 B = 516 B per
+// chunk, against 512 B for code_slot -- whose four-index groups a six-index
+// step would fill with a varying number of stores per step, and the writer's
+// counted waits need a fixed one.
+__host__ __device__ constexpr int kc_words(int J) { return (J + 1) / 2; }
+__host__ __device__ constexpr int kc_steps(int J) { return (CH + J - 1) / J; }
+// dword offset of step s of chunk c
+__host__ __device__ __forceinline__ size_t kc_slot(int64_t c, int s, int J) {
+  return (((size_t)(c >> 6) * kc_steps(J) + (size_t)s) * 64 + (size_t)(c & 63)) * kc_words(J);
+}
+__host__ __device__ __forceinline__ size_t kc_bytes(int64_t nch, int J) {
+  return (size_t)((nch + 63) >> 6) * kc_steps(J) * 64 * kc_words(J) * 4;
+}
+// One record (W dwords at a 4 W-byte-aligned address: one store / load).
+template <int W>
+__device__ __forceinline__ void kc_store(uint32_t *__restrict__ p, const uint32_t (&r)[W]) {
+  if constexpr (W == 2) {
+    *reinterpret_cast<uint2 *>(p) = make_uint2(r[0], r[1]);
+  } else if constexpr (W == 3) {
+    u32x3a4 v;
+    v.x = r[0]; v.y = r[1]; v.z = r[2];
+    *reinterpret_cast<u32x3a4 *>(p) = v;
+  } else {
+    static_assert(W == 4, "a record is 2 to 4 dwords");
+    *reinterpret_cast<uint4 *>(p) = make_uint4(r[0], r[1], r[2], r[3]);
+  }
+}
+template <int W>
+__device__ __forceinline__ void kc_load(const uint32_t *__restrict__ p, uint32_t (&r)[W]) {
+  if constexpr (W == 2) {
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);
+    r[0] = v.x; r[1] = v.y;
+  } else if constexpr (W == 3) {
+    const u32x3a4 v = *reinterpret_cast<const u32x3a4 *>(p);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z;
+  } else {
+    static_assert(W == 4, "a record is 2 to 4 dwords");
+    const uint4 v = *reinterpret_cast<const uint4 *>(p);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+  }
+}
+// The record of J codes (each < 2^16).
+template <int J>
+__device__ __forceinline__ void kc_pack(const uint32_t (&cs)[J], uint32_t (&r)[(J + 1) / 2]) {
+#pragma unroll
+  for (int q = 0; q < (J + 1) / 2; ++q) r[q] = cs[2 * q] | (2 * q + 1 < J ? cs[2 * q + 1] << 16 : 0u);
+}
+
 // Values of NV consecutive scan indices from a line table (ks_table
 // line_kind), OWN + 1 per line read: the line's own entries and the L1 entry
 // chosen by the next base (its first 16-32 B; lane-wise reads, for the
@@ -1597,12 +1650,19 @@ struct LaneBases {
 
 // kExact (compressed lines): xh holds the kept exact entries, and the lane
 // writes the chunk's Carry fields and verifies its exit (P1Lane::finish_exact).
-template <int OWN, bool kF64, bool kLdsLut, bool kTrlr, bool kExact = false>
+// kStore (kExact): every step's J codes go to the kept codes kc (kc_slot), one
+// store per step, issued after the step's lines of the step after next: the
+// stores join the in-order VM counter of the ring's loads, so a step's wait
+// lets pass the four loads of the next step and the two stores since (one or
+// none in the first two steps, two and no loads in the last).
+template <int OWN, bool kF64, bool kLdsLut, bool kTrlr, bool kExact = false, bool kStore = false>
 __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t total, int k, TableView tv,
                                                               EmitCfg ec, uint32_t *__restrict__ visits, P1 o,
                                                               Cand cand, const double *__restrict__ xh, SummP1 sp,
-                                                              Carry cr, unsigned int *__restrict__ err) {
+                                                              Carry cr, unsigned int *__restrict__ err,
+                                                              uint32_t *__restrict__ kc) {
   static_assert(!(kExact && kF64), "exact entries: compressed lines only");
+  static_assert(!kStore || (kExact && kLdsLut), "the kept codes are written from exact entries");
   constexpr int BS = kF64 ? 1024 : 768;  // 16 / 12 waves: ring 128 / 96 KiB (+ the LUT)
   constexpr int LV = kF64 ? 1 : 2;
   constexpr int J = OWN + LV;
@@ -1647,16 +1707,25 @@ __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t 
   };
   // keys of the step being processed and of the two in flight
   uint64_t x1 = 0, x2 = 0;
+  uint32_t *const kcl = kStore ? kc + kc_slot(live ? c : g.c0, 0, J) : nullptr;
   issue((uint32_t)(x >> (2 * LV)), 0);
   x1 = B.next_key(x, J, xmask);
   issue((uint32_t)(x1 >> (2 * LV)), 1);
   for (int st = 0; st < NS; ++st) {
     const uint64_t xs = x;  // key of this step
     // this step's lines complete (the next step's four loads may stay in flight)
-    if (st + 1 < NS) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (kStore) {
+      if (st + 1 >= NS) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      else if (st >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else if (st == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+      if (st + 1 < NS) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     const uint8_t *ln = ring + (st & 1) * 4096 + lane * 64;
     double v[J];
+    uint32_t rec[kc_words(J)] = {};
     if (!kF64) {
       uint32_t h[16];  // halfwords 0 .. 15 of the line (own + L1 <= 9 codes: 0 .. 8)
       const uint4 q0 = *reinterpret_cast<const uint4 *>(ln);
@@ -1675,6 +1744,7 @@ __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t 
       cs[OWN + 1] = *reinterpret_cast<const uint16_t *>(ln + 2 * (OWN + 4 + 4 * c1 + c2));
 #pragma unroll
       for (int t = 0; t < J; ++t) v[t] = kLut ? s_lut[cs[t]] : tv.lut[cs[t]];
+      if constexpr (kStore) kc_pack<J>(cs, rec);
     } else {
       const double *lv = reinterpret_cast<const double *>(ln);
 #pragma unroll
@@ -1689,6 +1759,9 @@ __global__ void __launch_bounds__(kF64 ? 1024 : 768) k_pass1l(Chunks g, int64_t 
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads are done before it is refilled
       issue((uint32_t)(x2 >> (2 * LV)), st & 1);
       x1 = x2;
+    }
+    if constexpr (kStore) {
+      if (live) kc_store<kc_words(J)>(kcl + (size_t)st * 64 * kc_words(J), rec);
     }
 #pragma unroll
     for (int t = 0; t < J; ++t) {
@@ -1734,12 +1807,17 @@ __device__ __forceinline__ void glds4(const void *gsrc, uint32_t lds) {
                : "memory");
 }
 
-// kExact: as k_pass1l's.
-template <int OWN, bool kTrlr, bool kExact = false>
+// kExact: as k_pass1l's.  kStore (kExact): a step's J codes, the escaped L3
+// code among them, go to the kept codes kc where the step is processed, one
+// iteration late: one store per step after the eight loads of the step after
+// next, so a step's wait lets pass those eight and the one store since (none in
+// the first two steps; in the last step and after the loop the one store).
+template <int OWN, bool kTrlr, bool kExact = false, bool kStore = false>
 __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
                                                        uint32_t *__restrict__ visits, P1 o, Cand cand,
                                                        const double *__restrict__ xh, SummP1 sp, Carry cr,
-                                                       unsigned int *__restrict__ err) {
+                                                       unsigned int *__restrict__ err, uint32_t *__restrict__ kc) {
+  static_assert(!kStore || kExact, "the kept codes are written from exact entries");
   constexpr int BS = kWideBlock;
   constexpr int J = OWN + 3;
   constexpr int NS = (CH + J - 1) / J;
@@ -1800,12 +1878,24 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
   double vp[J];
   uint64_t xp = 0;
   bool ep = false;
+  constexpr int KW = kc_words(J);
+  uint32_t *const kcl = kStore ? kc + kc_slot(live ? c : g.c0, 0, J) : nullptr;
+  uint32_t recp[KW] = {};  // kStore: the late step's record (its L3 code 0 where it escaped)
   auto process = [&](int sp_, const double *vv, uint64_t xk, bool e) {
     double v5 = vv[J - 1];
+    uint32_t c5 = 0;
     if (e) {  // the escaped L3 value: its code pair landed in the escape slot
       const uint32_t pr = esc[(sp_ & 1) * 64 + lane];
       const uint32_t km = (uint32_t)xk & kmask;
-      v5 = s_lut[(km & 1u) ? (pr >> 16) : (pr & 0xffffu)];
+      c5 = (km & 1u) ? (pr >> 16) : (pr & 0xffffu);
+      v5 = s_lut[c5];
+    }
+    if constexpr (kStore) {
+      uint32_t rec[KW];
+#pragma unroll
+      for (int q = 0; q < KW; ++q) rec[q] = recp[q];
+      rec[(J - 1) / 2] |= c5 << (16 * ((J - 1) & 1));
+      if (live) kc_store<KW>(kcl + (size_t)sp_ * 64 * KW, rec);
     }
 #pragma unroll
     for (int t = 0; t < J; ++t) {
@@ -1826,10 +1916,17 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
     const uint64_t xs = x;
     // this step's lines and the previous step's escape complete (the next
     // step's eight loads may stay in flight)
-    if (st + 1 < NS) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (kStore) {
+      if (st + 1 >= NS) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+      else if (st >= 2) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    } else {
+      if (st + 1 < NS) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     const uint8_t *ln = ring + (st & 1) * 2048 + lane * 32;  // the step's 8 dwords (dwords())
     double v[J];
+    uint32_t rec[KW] = {};
     bool e = false;
     {
       const uint4 q0 = *reinterpret_cast<const uint4 *>(ln);
@@ -1855,6 +1952,7 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
       cs[OWN + 2] = e ? 0u : c11;
 #pragma unroll
       for (int t = 0; t < J; ++t) v[t] = s_lut[cs[t]];
+      if constexpr (kStore) kc_pack<J>(cs, rec);
     }
     // this step's escape (every lane: a lane without one reads the first pair)
     {
@@ -1872,14 +1970,156 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
     if (st > 0) process(st - 1, vp, xp, ep);
 #pragma unroll
     for (int t = 0; t < J; ++t) vp[t] = v[t];
+    if constexpr (kStore) {
+#pragma unroll
+      for (int q = 0; q < KW; ++q) recp[q] = rec[q];
+    }
     xp = xs;
     ep = e;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // the last escape (kStore: the store after it may stay in flight)
+  if constexpr (kStore) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   process(NS - 1, vp, xp, ep);
   if (!live) return;
   if constexpr (kExact) L.finish_exact(c, g, o, cr, xh, err);
   else L.finish(c, o, sp);
+}
+
+// Pass 1 from the kept codes (ScanPlan::codes_read): a repeated scan of a
+// genome / table pair whose exact entries and per-index codes an earlier scan
+// left (k_pass1w / k_pass1l, kStore).  A lane streams its chunk's records
+// (kc_slot; a wave reads 64 W contiguous dwords per step, kCodeDepth steps
+// ahead), takes the values from the LUT in LDS and walks them as the exact
+// flavours of the line passes do: no key, no ring, no table read.  Packed
+// bases are read for the first k-mer of a run's first chunk (tr_lr), for the
+// visit histogram (kVisits: the line passes' key walk) and for the tripwire:
+// the first chunk of every 64 compares its first code with the base code
+// table's at its own k-mer (error bit 128).  A tripwire for codes that are not
+// the table's -- finish_exact still verifies every exact entry bit for bit
+// (bit 64), which catches a wrong code wherever the carried sum does not clamp
+// -- not a proof.
+constexpr int kCodeBlock = 1024;
+// steps per batch; one batch is loaded while the one before is walked.  2: at
+// most 64 VGPRs without the visit walk, so two 1024-lane blocks share a CU (8
+// waves per SIMD, 48 KB of records in flight per CU); 4 took 68-76.
+constexpr int kCodeDepth = 2;
+
+// The k-mer (k <= 15) of bases [p0, p0 + k) from the packed words.
+__device__ __forceinline__ uint32_t packed_kmer(const uint32_t *__restrict__ packed, int64_t total, int64_t p0, int k) {
+  const int64_t w0 = p0 >> 4, wlast = total >> 4;
+  const uint64_t x = ((uint64_t)packed[min(w0, wlast)] << 32) | packed[min(w0 + 1, wlast)];
+  const int sk = (int)(p0 & 15);
+  return (uint32_t)(x >> (64 - 2 * (sk + k))) & ((1u << (2 * k)) - 1u);
+}
+
+template <int J, bool kTrlr, bool kVisits>
+__global__ void __launch_bounds__(kCodeBlock) k_pass1c(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
+                                                       uint32_t *__restrict__ visits, P1 o, Cand cand,
+                                                       const double *__restrict__ xh, Carry cr,
+                                                       unsigned int *__restrict__ err,
+                                                       const uint32_t *__restrict__ kc) {
+  constexpr int NS = kc_steps(J), W = kc_words(J), D = kCodeDepth;
+  constexpr int NG = (NS + D - 1) / D;
+  extern __shared__ double s_clut[];
+  for (int i = threadIdx.x; i < tv.nlut; i += kCodeBlock) s_clut[i] = tv.lut[i];
+  __syncthreads();
+  const int64_t c = g.c0 + (int64_t)blockIdx.x * kCodeBlock + threadIdx.x;
+  if (c >= g.nch) return;
+  const int64_t start = g.start[c];
+  const int n = g.n[c];
+  const bool first = c == 0 || g.run[c - 1] != g.run[c];
+  const uint32_t kmask = (1u << (2 * k)) - 1u;
+  const uint32_t *__restrict__ rp = kc + kc_slot(c, 0, J);
+  uint32_t cur[D][W] = {}, nxt[D][W] = {};
+  auto fetch = [&](int gi, uint32_t (&b)[D][W]) {
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+      if (gi * D + d < NS) kc_load<W>(rp + (size_t)(gi * D + d) * 64 * W, b[d]);
+  };
+  fetch(0, cur);
+  P1Lane<false, kTrlr, true> L;
+  L.init(start, n, first, true, xh[c]);
+  // index i's k-mer: bases [start - k + i, start + i)
+  double first_val = 0.0;
+  if ((kTrlr && first) || (c & 63) == 0) {
+    const uint32_t km0 = packed_kmer(g.packed, total, start - k, k);
+    if (kTrlr && first) first_val = ec.ks[km0];
+    if ((c & 63) == 0 && (cur[0][0] & 0xffffu) != (uint32_t)tv.codes[km0]) atomicOr(err, 128u);
+  }
+  LaneBases B;
+  uint64_t x = 0;
+  const uint64_t xmask = (1ull << (2 * (k + J - 1))) - 1ull;
+  if (kVisits) {
+    B.load(g.packed, total, start - k);
+    x = B.first_key(k + J - 1);
+  }
+  for (int gi = 0; gi < NG; ++gi) {
+    if (gi + 1 < NG) fetch(gi + 1, nxt);
+    if (gi * D * J < n) {  // (a short chunk's later batches: nothing to walk)
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const int st = gi * D + d;
+        if (st < NS) {
+#pragma unroll
+          for (int t = 0; t < J; ++t) {
+            const int i = st * J + t;
+            if (i < n) {
+              const uint32_t code = (cur[d][t >> 1] >> (16 * (t & 1))) & 0xffffu;
+              double sv = s_clut[code];
+              if (kTrlr && first && i == 0) sv = first_val;
+              if (kVisits) atomicAdd(&visits[(uint32_t)(x >> (2 * (J - 1 - t))) & kmask], 1u);
+              L.step(sv, i, ec, cand);
+            }
+          }
+          if (kVisits) x = B.next_key(x, J, xmask);
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+#pragma unroll
+      for (int q = 0; q < W; ++q) cur[d][q] = nxt[d][q];
+  }
+  L.finish_exact(c, g, o, cr, xh, err);
+}
+
+// KS_TEST_KEPT_CODES (tests): the kept codes of a call that reads them, spoilt
+// before its pass 1.  what 0 (sample): the first code of chunk 0, which the
+// tripwire compares; 1 (all): every code; 2 (one): the code of index 1 of the
+// first chunk that no tripwire samples, that has a successor in its run (so
+// its exit is verified) and whose carried head the previous call -- its Carry
+// fields are still in the workspace -- found never to clamp; none: nothing is
+// spoilt and error bit 256 fails the call, so a test cannot pass on another
+// code than the one it asked for.  A spoilt code is 0, or 1 where it was 0:
+// another LUT entry, so another value.  One block.
+__global__ void __launch_bounds__(256) k_test_codes(uint32_t *__restrict__ kc, Chunks g, Carry cr, int64_t nch,
+                                                    int J, int what, unsigned int *__restrict__ err) {
+  auto spoil = [&](int64_t c, int i) {
+    uint32_t *p = kc + kc_slot(c, i / J, J) + (size_t)((i % J) >> 1);
+    const int sh = 16 * ((i % J) & 1);
+    const uint32_t code = (*p >> sh) & 0xffffu;
+    *p = (*p & ~(0xffffu << sh)) | ((code ? 0u : 1u) << sh);
+  };
+  if (what == 1) {
+    for (int64_t c = threadIdx.x; c < nch; c += blockDim.x)
+      for (int i = 0; i < CH; ++i) spoil(c, i);
+  } else if (what == 0) {
+    if (threadIdx.x == 0) spoil(0, 0);
+  } else {
+    __shared__ unsigned long long s_first;
+    if (threadIdx.x == 0) s_first = ~0ull;
+    __syncthreads();
+    for (int64_t c = threadIdx.x; c < nch; c += blockDim.x)
+      if ((c & 63) != 0 && g.n[c] > 1 && c + 1 < nch && g.run[c + 1] == g.run[c] && cr.mode[c] != kModeClean &&
+          cr.hq[c] < 0)
+        atomicMin(&s_first, (unsigned long long)c);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (s_first == ~0ull) atomicOr(err, 256u);
+      else spoil((int64_t)s_first, 1);
+    }
+  }
 }
 
 // Pass 1 over weighted-rank code lines (ks_table::d_rlines, line kind 4):
@@ -4154,7 +4394,49 @@ struct ScanPlan {
   //    the compressed line families' kernels (k_pass1w, k_pass1l); not with
   //    the diagnostics that read P2-P4 results, nor with the forced fallback.
   bool chunk_reuse, hint_reuse, entry_reuse;
+  // The kept codes (SLOT_CODE_KEEP; plan_codes, once the slot is there): a
+  // sub-mode of entry_reuse.  codes_J: the steps the form's line pass walks, 0:
+  // the form keeps no codes.  codes_write: the exact flavour of the line pass
+  // stores them (the first entry_reuse call that finds none: scan #2 of a genome
+  // / table pair); codes_read: k_pass1c streams them instead of reading lines.
+  int codes_J;
+  bool codes_write, codes_read;
 };
+
+// The OWN template argument of the compressed line passes for a table's
+// line_own (own 1..4 of the wide lines, 2..5 of the uint16 lines): the one
+// place pass1_half's dispatch and kept_codes_J take it from.
+template <class F>
+ks_status pick_wide_own(int own, F &&f) {
+  return pick_int<1, 3, 4>(own, f);
+}
+template <class F>
+ks_status pick_u16_own(int own, F &&f) {
+  return pick_int<3, 5, 2>(own, f);
+}
+
+// The steps of the line pass whose codes an indexed scan of this plan keeps,
+// 0: none (FP64 and rank tables, a LUT past the LDS copy, plain calls;
+// KS_NO_KEPT_CODES: off, for A/B runs and tests).
+int kept_codes_J(const ScanPlan &p, const TableView &tv, const ScanMode &mode) {
+  if (!mode.index || !p.p1summ || p.family != P1Family::Line || !p.comp || tv.nlut > kLineLutMax ||
+      getenv("KS_NO_KEPT_CODES") != nullptr)
+    return 0;
+  int J = 0;  // (k_pass1w: J = OWN + 3, k_pass1l on uint16 lines: J = OWN + 2)
+  if (tv.line_kind == 3)
+    (void)pick_wide_own(tv.line_own, [&](auto o) { J = decltype(o)::value + 3; return KS_OK; });
+  else
+    (void)pick_u16_own(tv.line_own, [&](auto o) { J = decltype(o)::value + 2; return KS_OK; });
+  return J;
+}
+
+// What the call does with the kept codes kc (null: the slot could not be had).
+void plan_codes(ScanPlan &p, const ChunkKeep &prev, const uint32_t *kc) {
+  // (the records lie by the kept chunk table's chunk index: not with KS_NO_CHUNK_REUSE)
+  const bool have = p.entry_reuse && p.chunk_reuse && kc != nullptr && p.codes_J != 0;
+  p.codes_read = have && prev.codes_ok && prev.codes_base == kc && prev.codes_J == p.codes_J;
+  p.codes_write = have && !p.codes_read;
+}
 
 // The plan of one call.  Reads every KS_* switch of this file (per call: tests
 // set them in-process between calls); makes no HIP call.  prev, kept: the kept
@@ -4298,6 +4580,7 @@ struct Work {
   TileComp tcomp;
   ReplayBuf rpb;  // likely-replay prefetch (k_marks_select lists, k_summ_fixw fills)
   uint16_t *codes = nullptr;  // ScanPlan::need_codes
+  uint32_t *kc = nullptr;     // the kept codes (SLOT_CODE_KEEP), null: none
   // Candidates and rescans in one list per half: the first half's are
   // emitted and rescanned while the second half is post-processed (a list
   // cannot be read while the other half's pass 1 still appends to it).
@@ -4482,15 +4765,27 @@ ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, con
                     cand, xh, sp1);
     case P1Family::Line: {
       const int own = tv.line_own;
+      if (plan.codes_read)  // the kept codes instead of the lines
+        return pick_int<5, 7, 4>(plan.codes_J, [&](auto j) {
+          return pick_bool(trlr, [&](auto t) {
+            return pick_bool(c.visits != nullptr, [&](auto v) {
+              return launch(k_pass1c<decltype(j)::value, decltype(t)::value, decltype(v)::value>, blocks(kCodeBlock),
+                            dim3(kCodeBlock), (size_t)tv.nlut * 8, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand,
+                            xh, cr, err, w.kc);
+            });
+          });
+        });
       if (tv.rline && !trlr && !plan.p1summ && own == 3)  // weighted-rank code lines (k = 13)
         return launch(k_pass1r<3>, blocks(kRankBlock), dim3(kRankBlock), 0, strm, gv, c.total, c.k, tv, ec, c.visits,
                       p1, cand);
       if (tv.line_kind == 3)  // wide lines: own 1..4 at k = 15..12 (J = 4..7)
-        return pick_int<1, 3, 4>(own, [&](auto o) {
+        return pick_wide_own(own, [&](auto o) {
           return pick_bool(trlr, [&](auto t) {
-            return pick_bool(plan.entry_reuse, [&](auto x) {
-              return launch(k_pass1w<decltype(o)::value, decltype(t)::value, decltype(x)::value>, blocks(kWideBlock),
-                            dim3(kWideBlock), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr, err);
+            return pick_int<1, 2, 0>(plan.entry_reuse ? (plan.codes_write ? 2 : 1) : 0, [&](auto x) {
+              return launch(k_pass1w<decltype(o)::value, decltype(t)::value, (decltype(x)::value > 0),
+                                     (decltype(x)::value > 1)>,
+                            blocks(kWideBlock), dim3(kWideBlock), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand,
+                            xh, sp1, cr, err, w.kc);
             });
           });
         });
@@ -4498,17 +4793,18 @@ ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, con
         return pick_int<3, 4, 2>(own, [&](auto o) {
           return pick_bool(trlr, [&](auto t) {
             return launch(k_pass1l<decltype(o)::value, true, false, decltype(t)::value>, blocks(1024), dim3(1024), 0,
-                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr, err);
+                          strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr, err, w.kc);
           });
         });
-      return pick_int<3, 5, 2>(own, [&](auto o) {
+      return pick_u16_own(own, [&](auto o) {
         return pick_bool(tv.nlut <= kLineLutMax, [&](auto l) {
           return pick_bool(trlr, [&](auto t) {
-            return pick_bool(plan.entry_reuse, [&](auto x) {
+            // (codes_write implies the LDS LUT, kept_codes_J)
+            return pick_int<1, 2, 0>(plan.entry_reuse ? (plan.codes_write ? 2 : 1) : 0, [&](auto x) {
               return launch(k_pass1l<decltype(o)::value, false, decltype(l)::value, decltype(t)::value,
-                                     decltype(x)::value>,
+                                     (decltype(x)::value > 0), (decltype(x)::value > 1 && decltype(l)::value)>,
                             blocks(768), dim3(768), 0, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand, xh, sp1, cr,
-                            err);
+                            err, w.kc);
             });
           });
         });
@@ -4754,8 +5050,33 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   const uint64_t ixid = mode.index ? mode.index->id : 0;
   const bool kept = ixid != 0 && prev.id == ixid && prev.k == k && prev.trlr == mode.trlr && prev.nch == nch &&
                     prev.ntiles == ntiles && prev.base == ksp;
-  const ScanPlan plan = plan_scan(tv, k, mode, runs, lay, prev, kept);
+  ScanPlan plan = plan_scan(tv, k, mode, runs, lay, prev, kept);
   const bool chunk_reuse = plan.chunk_reuse, hint_reuse = plan.hint_reuse, entry_reuse = plan.entry_reuse;
+  // ---- the kept codes: a slot of their own, sized by every indexed scan whose
+  // form keeps codes (so a fresh buffer is a first call's cost, never a
+  // repeated step's); without the memory the call goes on without the path
+  plan.codes_J = kept_codes_J(plan, tv, mode);
+  uint32_t *kcodes = nullptr;
+  if (plan.codes_J != 0) {
+    // a request the driver refused is not made again until the context's
+    // workspace went back (free_workspace): no hipMalloc of the whole slot per step
+    const size_t want = kc_bytes(nch, plan.codes_J);
+    void *p = nullptr;
+    const bool refused = ctx->code_keep_refused != 0 && want >= ctx->code_keep_refused &&
+                         ctx->slots[SLOT_CODE_KEEP].bytes < want;
+    if (!refused && getenv("KS_TEST_KEPT_CODES_NOMEM") == nullptr &&
+        ensure(ctx, SLOT_CODE_KEEP, want, &p) == KS_OK) {
+      kcodes = static_cast<uint32_t *>(p);
+    } else {
+      if (!refused && getenv("KS_TEST_KEPT_CODES_NOMEM") == nullptr) {
+        ctx->code_keep_refused = want;
+        (void)hipGetLastError();  // (a failed hipMalloc is not this call's error,
+        clear_last_error();       //  nor its message this call's)
+      }
+      ++mode.index->code_alloc_failures;
+    }
+  }
+  plan_codes(plan, prev, kcodes);
 
   // ---- workspace
   size_t bytes = 0;
@@ -4769,6 +5090,7 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   // with a sequence index the exact entries live in the kept slot: the carry
   // leaves them there for the next scan (entry_reuse: pass 1 reads them there)
   if (ixid != 0) w.cr.x = kp.entry;
+  w.kc = kcodes;
   w.p1.epoch = ++ctx->scan_epoch;
   unsigned long long *cnts = w.cnts;
   KS_HIP(hipMemsetAsync(cnts, 0, 8 * (2 * kSegs + 8), st));
@@ -4828,6 +5150,12 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
       // (w.pa, the predictor's sums, is free on this path: the copy the shift reads)
       if (what == 3) KS_HIP(hipMemcpyAsync(w.pa, spoilt, (size_t)nch * 8, hipMemcpyDeviceToDevice, st));
       KS_TRY(launch(k_test_hint, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, spoilt, w.pa, nch, what));
+    }
+    if (const char *tc = plan.codes_read ? getenv("KS_TEST_KEPT_CODES") : nullptr) {
+      const int what = !strcmp(tc, "sample") ? 0 : !strcmp(tc, "all") ? 1 : !strcmp(tc, "one") ? 2 : -1;
+      if (what < 0) return fail(KS_ERR_ARG, "KS_TEST_KEPT_CODES must be sample, all or one");
+      KS_TRY(launch(k_test_codes, dim3(1), dim3(256), 0, st, w.kc, w.g, w.cr, nch, plan.codes_J, what,
+                    reinterpret_cast<unsigned int *>(cnts + 2 * kSegs + 1)));
     }
   } else if (plan.p1summ) {
     // the first half's predictor and prescan first (they gate its pass 1;
@@ -4943,15 +5271,20 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   if (errbits & 32u)
     return fail(KS_ERR_DEVICE, "chunked scan epoch check failed: the stitch read pass-1 results not written by this "
                                  "call (epoch %u)", w.p1.epoch);
-  if (entry_reuse && (errbits & 64u)) {
+  if (entry_reuse && (errbits & (64u | 128u))) {
     // a kept entry was not the exact exit of the chunk before it: nothing of
     // this attempt counts (scan_core resets the region counters and the
     // scratch visit histogram per attempt).  The slot's chunk table and P2 hint
     // were not written, so the tag goes back without entry_ok and the rerun
     // takes the hint path, whose carry rewrites every entry.
+    // Bit 128: a sampled kept code was not the table's (k_pass1c).  Either bit
+    // on a call that read the codes takes them away too: the next call from
+    // exact entries writes them again.
     ctx->chunk_keep = prev;
     ctx->chunk_keep.entry_ok = false;
+    if (plan.codes_read || plan.codes_write) ctx->chunk_keep.codes_ok = false;
     if (mode.index) ++mode.index->entry_fallbacks;
+    if (mode.index && plan.codes_read) ++mode.index->code_fallbacks;
     return KS_INTERNAL_RETRY;
   }
   if (errbits & ~16u) return fail(KS_ERR_INTERNAL, "chunked scan consistency check failed (bits %u)", errbits);
@@ -4980,7 +5313,18 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
     // every chunk's entry (general path) or pass 1 verified every one.
     ctx->chunk_keep = ChunkKeep{ixid, k, mode.trlr, nch, ntiles, ksp, mode.table_id, mode.init_id,
                                 entry_reuse ? prev.hint : 1 - hx, true};
+    // the kept codes: written or read and verified by this call, or left as they
+    // were by a call from exact entries that went without them; any other call
+    // (another table, the general path) leaves none
+    if (entry_reuse) {
+      const bool used = plan.codes_read || plan.codes_write;
+      ctx->chunk_keep.codes_ok = used || prev.codes_ok;
+      ctx->chunk_keep.codes_base = used ? kcodes : prev.codes_base;
+      ctx->chunk_keep.codes_J = used ? plan.codes_J : prev.codes_J;
+    }
     ks_seq_index *ix = mode.index;
+    if (plan.codes_write) ++ix->code_builds;
+    if (plan.codes_read) ++ix->code_reuses;
     if (chunk_reuse) ++ix->chunk_reuses;
     if (hint_reuse) ++ix->hint_reuses;
     if (entry_reuse) ++ix->entry_reuses;
@@ -4988,6 +5332,57 @@ ks_status scan_chunked(ks_ctx *ctx, const ks_dev_seqs *s, const Runs &runs, cons
   }
   return KS_OK;
 }
+
+}  // namespace ks
+
+// Where the kept codes keep scan index i of chunk c of nch, in steps of J:
+// the slot's bytes and the index's halfword offset (host arithmetic only).
+extern "C" ks_status ks_kept_codes_layout(int32_t J, int64_t nch, int64_t c, int32_t i, int64_t *bytes,
+                                          int64_t *halfword) {
+  using namespace ks;
+  if (J < 2 || J > 8 || nch < 0 || c < 0 || c >= std::max<int64_t>(nch, 1) || i < 0 || i >= CH || !bytes || !halfword)
+    return fail(KS_ERR_ARG, "ks_kept_codes_layout: bad argument");
+  *bytes = (int64_t)kc_bytes(nch, J);
+  *halfword = (int64_t)(kc_slot(c, i / J, J) * 2 + (size_t)(i % J));
+  return KS_OK;
+}
+
+// Test-only read window (as ks_table_debug_read): the kept codes of chunks
+// [c0, c0 + nchunks) of the context's last chunked scan, in index order, 256
+// per chunk -- a copy to the host and a host reorder, no kernel and no device
+// write.  KS_ERR_ARG when the context keeps no codes.
+extern "C" ks_status ks_kept_codes_debug_read(ks_ctx *ctx, int64_t c0, int64_t nchunks, uint16_t *dst_host,
+                                              int32_t *steps_J) {
+  using namespace ks;
+  if (!ctx) ctx = ks_default_ctx();
+  if (!ctx || !dst_host) return fail(KS_ERR_ARG, "ks_kept_codes_debug_read: null argument");
+  const ChunkKeep &kk = ctx->chunk_keep;
+  if (kk.id == 0 || !kk.codes_ok || kk.codes_base != ctx->slots[SLOT_CODE_KEEP].ptr || kk.codes_J == 0)
+    return fail(KS_ERR_ARG, "ks_kept_codes_debug_read: the context keeps no codes");
+  if (c0 < 0 || nchunks < 0 || c0 > kk.nch || nchunks > kk.nch - c0)
+    return fail(KS_ERR_ARG, "ks_kept_codes_debug_read: chunks [%lld, %lld + %lld) outside the scan's %lld",
+                (long long)c0, (long long)c0, (long long)nchunks, (long long)kk.nch);
+  if (steps_J) *steps_J = kk.codes_J;
+  if (nchunks == 0) return KS_OK;
+  const int J = kk.codes_J;
+  const int64_t t0 = c0 >> 6, t1 = (c0 + nchunks + 63) >> 6;
+  const size_t tile_dw = (size_t)kc_steps(J) * 64 * kc_words(J);
+  std::vector<uint32_t> h((size_t)(t1 - t0) * tile_dw);
+  int cur = -1;
+  KS_HIP(hipGetDevice(&cur));
+  KS_HIP(hipSetDevice(ctx->device));
+  const hipError_t e = hipMemcpy(h.data(), static_cast<const uint32_t *>(kk.codes_base) + (size_t)t0 * tile_dw,
+                                 h.size() * 4, hipMemcpyDeviceToHost);
+  if (cur >= 0) (void)hipSetDevice(cur);
+  KS_HIP(e);
+  const uint16_t *hh = reinterpret_cast<const uint16_t *>(h.data());
+  for (int64_t c = c0; c < c0 + nchunks; ++c)
+    for (int i = 0; i < CH; ++i)
+      dst_host[(size_t)(c - c0) * CH + i] = hh[(kc_slot(c, i / J, J) - (size_t)t0 * tile_dw) * 2 + (size_t)(i % J)];
+  return KS_OK;
+}
+
+namespace ks {
 
 // Phase times of the last chunked scan on ctx (its events are complete once
 // the caller has synchronised after the region readback).

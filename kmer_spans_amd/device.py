@@ -54,6 +54,19 @@ class SeqIndex:
         check(fn(self._h, C.byref(r), C.byref(f)))
         return {"entry_reuses": int(r.value), "entry_fallbacks": int(f.value)}
 
+    def codes_info(self) -> dict:
+        """The kept per-index codes: scans that wrote them (code_builds), scans
+        that streamed them instead of reading table lines (code_reuses), reading
+        calls rerun on the hint path (code_fallbacks) and calls that went
+        without the slot for want of memory (code_alloc_failures)."""
+        fn = load().ks_seq_index_codes_info
+        fn.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
+        fn.restype = C.c_int32
+        v = [C.c_int64() for _ in range(4)]
+        check(fn(self._h, *[C.byref(x) for x in v]))
+        names = ("code_builds", "code_reuses", "code_fallbacks", "code_alloc_failures")
+        return {n: int(x.value) for n, x in zip(names, v)}
+
     def close(self):
         if self._h:
             load().ks_seq_index_destroy(self._h)
@@ -275,6 +288,30 @@ class DeviceTable:
             self.close()
         except Exception:
             pass
+
+
+def kept_codes_layout(J: int, nch: int, c: int, i: int) -> tuple[int, int]:
+    """ks_kept_codes_layout: (bytes of the kept codes of nch chunks in steps of
+    J, halfword offset of scan index i of chunk c).  Host arithmetic only."""
+    fn = load().ks_kept_codes_layout
+    fn.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    fn.restype = C.c_int32
+    b, h = C.c_int64(), C.c_int64()
+    check(fn(int(J), int(nch), int(c), int(i), C.byref(b), C.byref(h)))
+    return int(b.value), int(h.value)
+
+
+def kept_codes_read(ctx: _lib.Context, c0: int, nchunks: int) -> tuple[np.ndarray, int]:
+    """ks_kept_codes_debug_read: the kept codes of chunks [c0, c0 + nchunks) of
+    ctx's last chunked scan as uint16 [nchunks, 256] in index order, and the
+    step J they were written in (tests)."""
+    fn = load().ks_kept_codes_debug_read
+    fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int32)]
+    fn.restype = C.c_int32
+    out = np.zeros((int(nchunks), 256), dtype=np.uint16)
+    j = C.c_int32()
+    check(fn(ctx.handle if ctx is not None else None, int(c0), int(nchunks), out.ctypes.data, C.byref(j)))
+    return out, int(j.value)
 
 
 def bind_torch_stream(ctx: _lib.Context) -> None:

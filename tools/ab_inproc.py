@@ -42,7 +42,15 @@ def main():
     p.add_argument("--table-per-variant", action="store_true",
                    help="build one table per variant with its environment set (table-form A/Bs: KS_NO_LINES, "
                         "KS_NO_WIDE_LINES); all tables stay resident")
+    p.add_argument("--visits", action="store_true",
+                   help="every step fills the visit histogram (zeroed outside the timed part), and every variant's "
+                        "histogram must equal the first variant's")
+    p.add_argument("--trlr", action="store_true",
+                   help="tr_lr scans (min_length 100) with the table as transition table and a fixed random "
+                        "first-k-mer table")
     a = p.parse_args()
+    if a.visits and a.trlr:
+        p.error("--visits and --trlr exclude each other (tr_lr has no visit histogram)")
     import numpy as np
     import torch
     from kmer_spans_amd import _lib, device as D, genome
@@ -81,6 +89,12 @@ def main():
         mine = max(shards, key=lambda sh: sum(int(lens[q]) for q in sh))
         ds = ds.subset(sorted(mine))
         print("shard", a.shard_of, "contigs", sorted(mine), "bp", int(ds.total), flush=True)
+    init = None
+    if a.trlr:
+        init = D.DeviceTable(ctx, np.random.default_rng(3).normal(size=4 ** a.k), a.k, 0.0, compress=False,
+                             expand=False)
+    vis = torch.zeros(4 ** a.k, dtype=torch.int32, device="cuda") if a.visits else None
+    ref_vis = None
     res = {n: [] for n, _ in variants}
     rounds = {n: [] for n, _ in variants}  # per-round median step
     runs_ms = {n: [] for n, _ in variants}  # ms_runs of every kept step
@@ -97,9 +111,14 @@ def main():
             try:
                 kept = []
                 for i_step in range(a.steps + a.discard):
+                    if vis is not None:
+                        vis.zero_()
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    pos, sc, st = D.scan(ctx, ds, a.k, tabs.get(name, tab), 100, 20.0)
+                    if a.trlr:
+                        pos, sc, st = D.tr_lr(ctx, ds, a.k, tabs.get(name, tab), init, 100)
+                    else:
+                        pos, sc, st = D.scan(ctx, ds, a.k, tabs.get(name, tab), 100, 20.0, vis)
                     torch.cuda.synchronize()
                     ms = (time.perf_counter() - t0) * 1e3
                     if i_step >= a.discard and r >= 0:
@@ -114,6 +133,12 @@ def main():
                         ref = (pos.copy(), np.ascontiguousarray(sc).copy())
                     elif not (np.array_equal(pos, ref[0]) and np.array_equal(sc, ref[1])):
                         raise SystemExit(f"variant {name}: regions differ from the first variant's")
+                    if vis is not None:
+                        hv = vis.cpu().numpy()
+                        if ref_vis is None:
+                            ref_vis = hv.copy()
+                        elif not np.array_equal(hv, ref_vis):
+                            raise SystemExit(f"variant {name}: the visit histogram differs from the first variant's")
                 if r >= 0:
                     rounds[name].append(statistics.median(kept))
             finally:
@@ -136,7 +161,7 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
-    for t_ in set(list(tabs.values()) + [tab]):
+    for t_ in set(list(tabs.values()) + [tab] + ([init] if init is not None else [])):
         t_.close()
 
 
