@@ -158,8 +158,9 @@ int64_t ks_shard_plan(const char *const *seqs, const int64_t *lens, int32_t nseq
                       int64_t *out, int64_t cap);
 /* Phases of the last multi-device call (ms, host wall clock), into out[cap]:
  * [0] whole call, [1] the parts' first phase (kmer_counts / kmer_regions: the
- * whole per-device body; low_comp: staging + count), [2] the host-side sum of
- * the count / visit histograms, [3] low_comp: rank table + scan, [4] region
+ * whole per-device body; low_comp: staging + count), [2] the sum of the count
+ * / visit histograms (on the host; low_comp: the count sum on the devices, a
+ * reduce-scatter and an all-gather of stripes), [3] low_comp: rank table + scan, [4] region
  * merge, [5] parts P, then per part p: [6 + 4p] body, [7 + 4p] staging +
  * count, [8 + 4p] score-table upload + compression, [9 + 4p] scan
  * (kmer_regions only).  Returns the number of values available. */

@@ -35,16 +35,21 @@ class DevSeqs(C.Structure):
                 ("nseq", C.c_int32)]
 
 
-class ScanStats(C.Structure):
+class Stats(C.Structure):
+    """Base of the statistics blocks the library fills in: a subclass gives
+    only its _fields_ (the header's, in order)."""
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class ScanStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_runs", C.c_double), ("ms_scan", C.c_double),
                 ("ms_rescan", C.c_double), ("ms_finish", C.c_double), ("n_bases", C.c_int64),
                 ("n_scored", C.c_int64), ("n_runs", C.c_int64), ("n_regions", C.c_int64),
                 ("n_rescan", C.c_int64), ("scan_algo", C.c_int32),
                 ("n_replay", C.c_int64), ("ms_layout", C.c_double), ("ms_predict", C.c_double),
                 ("ms_carry", C.c_double), ("ms_stitch", C.c_double)]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class SeqIndexInfo(C.Structure):
@@ -58,24 +63,18 @@ class SeqIndexInfo(C.Structure):
         return {f: int(getattr(self, f)) for f in (fields or [f for f, _ in self._fields_])}
 
 
-class TableInfo(C.Structure):
+class TableInfo(Stats):
     _fields_ = [("k", C.c_int32), ("compressed", C.c_int32), ("positions_per_read", C.c_int32),
                 ("code_bits", C.c_int32), ("distinct", C.c_int64), ("ext_bytes", C.c_int64),
                 ("escape_fraction", C.c_double), ("ms_upload", C.c_double), ("ms_compress", C.c_double),
                 ("ms_codes12", C.c_double), ("ms_ext_alloc", C.c_double), ("ms_ext_build", C.c_double),
                 ("ms_total", C.c_double), ("line_kind", C.c_int32), ("line_own", C.c_int32)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class TableProps(C.Structure):
+class TableProps(Stats):
     _fields_ = [("int_exact", C.c_int32), ("no_nan_posinf", C.c_int32), ("max_abs", C.c_double),
                 ("ext_J", C.c_int32), ("ext_bits", C.c_int32), ("line_kind", C.c_int32), ("line_own", C.c_int32),
                 ("approx_k", C.c_int32), ("n_rpieces", C.c_int32)]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 # KS_TABLE_PART_* of ks_table_debug_bytes / ks_table_debug_read, with the element type of each part
@@ -84,73 +83,49 @@ TABLE_PARTS = {"vals": (0, np.float64), "codes": (1, np.uint16), "lut": (2, np.f
                "map12": (7, np.uint16), "approx": (8, np.uint16)}
 
 
-class SpectraStats(C.Structure):
+class SpectraStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_plan", C.c_double), ("ms_count", C.c_double),
                 ("ms_entropy", C.c_double), ("n_regions", C.c_int64), ("n_bases", C.c_int64),
                 ("n_words", C.c_int64), ("n_tiles", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class DistStats(C.Structure):
+class DistStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_distance", C.c_double),
                 ("n_pairs", C.c_int64), ("bytes_written", C.c_int64), ("panel_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class HclustStats(C.Structure):
+class HclustStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_init", C.c_double),
                 ("ms_merge", C.c_double), ("n", C.c_int64), ("n_rescans", C.c_int64), ("work_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class NjStats(C.Structure):
+class NjStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_init", C.c_double),
                 ("ms_join", C.c_double), ("n", C.c_int64), ("n_compactions", C.c_int64), ("work_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class SilhouetteStats(C.Structure):
+class SilhouetteStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_check", C.c_double), ("ms_sums", C.c_double),
                 ("ms_widths", C.c_double), ("n", C.c_int64), ("ngroups", C.c_int64), ("n_chunks", C.c_int64),
                 ("work_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class PcaStats(C.Structure):
+class PcaStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_gram", C.c_double),
                 ("ms_eigen", C.c_double), ("ms_project", C.c_double), ("n_sweeps", C.c_int64),
                 ("n_rotations", C.c_int64), ("panel_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class KmeansStats(C.Structure):
+class KmeansStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_assign", C.c_double),
                 ("ms_update", C.c_double), ("ms_wss", C.c_double), ("n_iter", C.c_int64),
                 ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
 
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
-
-class KnnStats(C.Structure):
+class KnnStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_select", C.c_double),
                 ("ms_merge", C.c_double), ("n_splits", C.c_int64), ("tiles_per_split", C.c_int64),
                 ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class KmeansResult(C.Structure):
@@ -162,12 +137,9 @@ class SeedResult(C.Structure):
                 ("radius", C.c_double), ("far_row", C.c_int64)]
 
 
-class SeedStats(C.Structure):
+class SeedStats(Stats):
     _fields_ = [("ms_total", C.c_double), ("ms_normalise", C.c_double), ("ms_steps", C.c_double),
                 ("n_launches", C.c_int64), ("panel_bytes", C.c_int64), ("work_bytes", C.c_int64)]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class Fasta(C.Structure):
@@ -185,37 +157,6 @@ class KmerFileInfo(C.Structure):
     _fields_ = [("written", C.c_int32), ("seq_size", C.c_double), ("seq_fsize", C.c_double),
                 ("seq_fl", C.c_double), ("out_path", C.c_char * 4096), ("message", C.c_char * 512)]
 
-
-# Every symbol include/kmer_spans.h declares (tests check they are exported).
-EXPORTS = [
-    "ks_last_error", "ks_version", "ks_regions_free", "ks_ctx_create", "ks_ctx_destroy",
-    "ks_ctx_set_stream", "ks_default_ctx", "ks_kmer_counts", "ks_kmer_regions",
-    "ks_low_comp_regions", "ks_kmer_seq", "ks_rank_table", "ks_log2_table", "ks_pm1_table",
-    "ks_table_create", "ks_table_destroy", "ks_table_is_compressed", "ks_table_distinct",
-    "ks_table_positions_per_read", "ks_table_create_hint", "ks_table_code_bits", "ks_table_escape_fraction",
-    "ks_table_get_info", "ks_table_debug_bytes", "ks_table_debug_read", "ks_table_debug_props",
-    "ks_scan_dev", "ks_count_dev", "ks_ctx_set_scan_algo", "ks_tr_lr_regions", "ks_tr_lr_dev",
-    "ks_fasta_load", "ks_fasta_parse", "ks_fasta_copy_seqs", "ks_fasta_free", "ks_count_multi_dev",
-    "ks_count_file_write", "ks_count_file_read", "ks_count_file_free", "ks_kmers_to_file",
-    "ks_windowed_dist", "ks_windowed_dev", "ks_table_from_counts",
-    "ks_release_cache", "ks_set_fork_broker", "ks_set_host_cache",
-    "ks_set_devices", "ks_get_devices", "ks_shard_plan", "ks_merge_parts", "ks_set_host_cache_idle",
-    "ks_multi_last_stats",
-    "ks_region_spectra", "ks_region_spectra_dev", "ks_spectra_tile_bases",
-    "ks_spectra_dist", "ks_spectra_dist_dev", "ks_spectra_cross_dist", "ks_spectra_cross_dist_dev",
-    "ks_dist_pair_offsets", "ks_dist_tiles_of", "ks_dist_tile_rows",
-    "ks_hclust", "ks_hclust_dev", "ks_hclust_cut",
-    "ks_nj", "ks_nj_dev", "ks_nj_edges",
-    "ks_silhouette", "ks_silhouette_dev",
-    "ks_spectra_pca", "ks_spectra_pca_dev", "ks_pca_round_pairs",
-    "ks_spectra_kmeans", "ks_spectra_kmeans_dev", "ks_spectra_group_means", "ks_spectra_group_means_dev",
-    "ks_spectra_kmeans_seed", "ks_spectra_kmeans_seed_dev",
-    "ks_spectra_knn", "ks_spectra_knn_dev",
-    "ks_seq_index_create", "ks_seq_index_destroy", "ks_seq_index_info_get", "ks_seq_index_entry_info",
-    "ks_seq_index_codes_info", "ks_kept_codes_layout", "ks_kept_codes_debug_read",
-    "ks_scan_dev_indexed", "ks_tr_lr_dev_indexed",
-    "ks_scan_chunk_indices", "ks_scan_tile_chunks",
-]
 
 KS_SPECTRA_MAX_Q = 6
 KS_SPECTRA_BOTH_STRANDS = 1
@@ -236,7 +177,118 @@ SEED_METHODS = {"maximin": 0, "kmeans++": 1}  # KS_SEED_MAXIMIN, KS_SEED_DSQ
 
 SCORES = {"log2": 1, "pm1": 2, "rank": 3}  # KS_SCORE_* of ks_table_from_counts
 
+# The C ABI: name -> (argtypes, restype) of every function include/kmer_spans.h
+# declares.  Written by hand; tests/test_bindings.py parses the header and
+# compares the arity and the kind of every parameter and return value.  A
+# pointer of any type is P (a numpy address, a data_ptr(), a byref()).
+P, I32, I64, D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+SIGNATURES = {
+    "ks_last_error": ([], C.c_char_p),
+    "ks_version": ([], C.c_char_p),
+    "ks_regions_free": ([P], None),
+    "ks_ctx_create": ([I32, P], I32),
+    "ks_ctx_destroy": ([P], None),
+    "ks_ctx_set_stream": ([P, P], I32),
+    "ks_default_ctx": ([], P),
+    "ks_ctx_set_scan_algo": ([P, I32], I32),
+    "ks_kmer_counts": ([P, P, P, I32, I32, P, P], I32),
+    "ks_kmer_regions": ([P, P, P, I32, I32, P, I64, I32, D, P, P, P], I32),
+    "ks_low_comp_regions": ([P, P, P, I32, I32, I32, D, D, P, P, P, P], I32),
+    "ks_kmer_seq": ([I32, P, C.c_size_t], I32),
+    "ks_rank_table": ([P, I32, D, P], I32),
+    "ks_log2_table": ([P, I32, P], I32),
+    "ks_pm1_table": ([P, I32, P], I32),
+    "ks_table_create": ([P, P, I32, D, I32, P], I32),
+    "ks_table_destroy": ([P], None),
+    "ks_table_is_compressed": ([P], I32),
+    "ks_table_distinct": ([P], I64),
+    "ks_table_positions_per_read": ([P], I32),
+    "ks_table_create_hint": ([P, P, I32, D, I32, P, P], I32),
+    "ks_table_code_bits": ([P], I32),
+    "ks_table_escape_fraction": ([P], D),
+    "ks_table_get_info": ([P, P], I32),
+    "ks_table_debug_bytes": ([P, I32], I64),
+    "ks_table_debug_read": ([P, I32, I64, I64, P], I32),
+    "ks_table_debug_props": ([P, P], I32),
+    "ks_scan_dev": ([P, P, I32, P, I32, D, P, P, P], I32),
+    "ks_count_dev": ([P, P, I32, P, P], I32),
+    "ks_tr_lr_regions": ([P, P, P, I32, I32, I32, P, P, P, I64, P, P], I32),
+    "ks_tr_lr_dev": ([P, P, I32, P, P, I32, P, P], I32),
+    "ks_fasta_load": ([P, C.c_char_p, I64, P], I32),
+    "ks_fasta_parse": ([P, C.c_char_p, I64, I64, P], I32),
+    "ks_fasta_copy_seqs": ([P, P], I32),
+    "ks_fasta_free": ([P], None),
+    "ks_count_multi_dev": ([P, P, P, I32, P, P], I32),
+    "ks_count_file_write": ([C.c_char_p, I32, I32, P, P], I32),
+    "ks_count_file_read": ([C.c_char_p, I32, P], I32),
+    "ks_count_file_free": ([P], None),
+    "ks_kmers_to_file": ([P, C.c_char_p, C.c_char_p, P, I32, D, I32, P], I32),
+    "ks_windowed_dist": ([P, P, P, I32, P, I32, I32, I32, I32, P, P, P], I32),
+    "ks_windowed_dev": ([P, P, P, I32, I32, I32, P, P, P], I32),
+    "ks_table_from_counts": ([P, P, I32, I32, D, D, I32, I64, P, P], I32),
+    "ks_release_cache": ([], None),
+    "ks_set_fork_broker": ([I32], I32),
+    "ks_set_host_cache": ([I32], I32),
+    "ks_set_devices": ([P, I32], I32),
+    "ks_set_host_cache_idle": ([D], I32),
+    "ks_get_devices": ([P, I32], I32),
+    "ks_shard_plan": ([P, P, I32, I32, P, I64], I64),
+    "ks_merge_parts": ([P, I64, I32, P, P], I32),
+    "ks_multi_last_stats": ([P, I32], I32),
+    "ks_region_spectra": ([P, P, P, I32, P, P, P, I64, I32, I32, P, P], I32),
+    "ks_region_spectra_dev": ([P, P, P, P, P, I64, I32, I32, P, P, P], I32),
+    "ks_spectra_tile_bases": ([], I32),
+    "ks_spectra_dist": ([P, P, I64, I32, P, I64, I32, P], I32),
+    "ks_spectra_dist_dev": ([P, P, I64, I32, P, I64, I32, P, P], I32),
+    "ks_spectra_cross_dist": ([P, P, I64, I32, P, I64, P, I64, I32, P], I32),
+    "ks_spectra_cross_dist_dev": ([P, P, I64, I32, P, I64, P, I64, I32, P, P], I32),
+    "ks_dist_pair_offsets": ([P, P, I64, I64, P], None),
+    "ks_dist_tiles_of": ([P, I64, I64, P, P], None),
+    "ks_dist_tile_rows": ([], I32),
+    "ks_hclust": ([P, P, I64, I32, P, P, P], I32),
+    "ks_hclust_dev": ([P, P, I64, I32, I32, P, P, P, P], I32),
+    "ks_hclust_cut": ([P, P, I64, I32, D, P], I32),
+    "ks_nj": ([P, P, I64, P, P, P, P], I32),
+    "ks_nj_dev": ([P, P, I64, I32, P, P, P, P, P], I32),
+    "ks_nj_edges": ([P, P, P, P, I64, P, P], I32),
+    "ks_silhouette": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P], I32),
+    "ks_silhouette_dev": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P], I32),
+    "ks_spectra_pca": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P], I32),
+    "ks_spectra_pca_dev": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P, P], I32),
+    "ks_pca_round_pairs": ([I32, I32, P, P], I32),
+    "ks_spectra_kmeans": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P], I32),
+    "ks_spectra_kmeans_dev": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P, P], I32),
+    "ks_spectra_group_means": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P], I32),
+    "ks_spectra_group_means_dev": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P, P], I32),
+    "ks_spectra_kmeans_seed": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P], I32),
+    "ks_spectra_kmeans_seed_dev": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P, P], I32),
+    "ks_spectra_knn": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P], I32),
+    "ks_spectra_knn_dev": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P, P], I32),
+    "ks_seq_index_create": ([P, P], I32),
+    "ks_seq_index_destroy": ([P], None),
+    "ks_seq_index_info_get": ([P, P], I32),
+    "ks_seq_index_entry_info": ([P, P, P], I32),
+    "ks_seq_index_codes_info": ([P, P, P, P, P], I32),
+    "ks_kept_codes_layout": ([I32, I64, I64, I32, P, P], I32),
+    "ks_kept_codes_debug_read": ([P, I64, I64, P, P], I32),
+    "ks_scan_dev_indexed": ([P, P, P, I32, P, I32, D, P, P, P], I32),
+    "ks_tr_lr_dev_indexed": ([P, P, P, I32, P, P, I32, P, P], I32),
+    "ks_scan_chunk_indices": ([], I32),
+    "ks_scan_tile_chunks": ([], I32),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
+
+
+def _type_library(L, table=SIGNATURES):
+    """Set argtypes and restype of every table entry L has.  A name L lacks is
+    skipped (KS_LIB_PATH may name an earlier build, for A/B runs, without a
+    newer symbol); calling it fails at the call."""
+    for name, (args, res) in table.items():
+        f = getattr(L, name, None)
+        if f is not None:
+            f.argtypes, f.restype = args, res
 
 
 def load():
@@ -247,101 +299,7 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: run __graft_entry__.build() (no CPU fallback exists)")
     L = C.CDLL(LIB_PATH)
-    P, I32, I64, D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    sigs = {
-        "ks_last_error": ([], C.c_char_p),
-        "ks_version": ([], C.c_char_p),
-        "ks_regions_free": ([P], None),
-        "ks_ctx_create": ([I32, P], I32),
-        "ks_ctx_destroy": ([P], None),
-        "ks_ctx_set_stream": ([P, P], I32),
-        "ks_default_ctx": ([], P),
-        "ks_ctx_set_scan_algo": ([P, I32], I32),
-        "ks_kmer_counts": ([P, P, P, I32, I32, P, P], I32),
-        "ks_kmer_regions": ([P, P, P, I32, I32, P, I64, I32, D, P, P, P], I32),
-        "ks_low_comp_regions": ([P, P, P, I32, I32, I32, D, D, P, P, P, P], I32),
-        "ks_kmer_seq": ([I32, P, C.c_size_t], I32),
-        "ks_rank_table": ([P, I32, D, P], I32),
-        "ks_log2_table": ([P, I32, P], I32),
-        "ks_pm1_table": ([P, I32, P], I32),
-        "ks_table_create": ([P, P, I32, D, I32, P], I32),
-        "ks_table_destroy": ([P], None),
-        "ks_table_is_compressed": ([P], I32),
-        "ks_table_distinct": ([P], I64),
-        "ks_table_positions_per_read": ([P], I32),
-        "ks_table_create_hint": ([P, P, I32, D, I32, P, P], I32),
-        "ks_table_code_bits": ([P], I32),
-        "ks_table_escape_fraction": ([P], D),
-        "ks_table_get_info": ([P, P], I32),
-        "ks_table_debug_bytes": ([P, I32], I64),
-        "ks_table_debug_read": ([P, I32, I64, I64, P], I32),
-        "ks_table_debug_props": ([P, P], I32),
-        "ks_scan_dev": ([P, P, I32, P, I32, D, P, P, P], I32),
-        "ks_count_dev": ([P, P, I32, P, P], I32),
-        "ks_tr_lr_regions": ([P, P, P, I32, I32, I32, P, P, P, I64, P, P], I32),
-        "ks_tr_lr_dev": ([P, P, I32, P, P, I32, P, P], I32),
-        "ks_fasta_load": ([P, C.c_char_p, I64, P], I32),
-        "ks_fasta_parse": ([P, C.c_char_p, I64, I64, P], I32),
-        "ks_fasta_copy_seqs": ([P, P], I32),
-        "ks_fasta_free": ([P], None),
-        "ks_count_multi_dev": ([P, P, P, I32, P, P], I32),
-        "ks_count_file_write": ([C.c_char_p, I32, I32, P, P], I32),
-        "ks_count_file_read": ([C.c_char_p, I32, P], I32),
-        "ks_count_file_free": ([P], None),
-        "ks_kmers_to_file": ([P, C.c_char_p, C.c_char_p, P, I32, D, I32, P], I32),
-        "ks_windowed_dist": ([P, P, P, I32, P, I32, I32, I32, I32, P, P, P], I32),
-        "ks_windowed_dev": ([P, P, P, I32, I32, I32, P, P, P], I32),
-        "ks_table_from_counts": ([P, P, I32, I32, D, D, I32, I64, P, P], I32),
-        "ks_release_cache": ([], None),
-        "ks_set_fork_broker": ([I32], I32),
-        "ks_set_host_cache": ([I32], I32),
-        "ks_set_devices": ([P, I32], I32),
-        "ks_set_host_cache_idle": ([D], I32),
-        "ks_get_devices": ([P, I32], I32),
-        "ks_shard_plan": ([P, P, I32, I32, P, I64], I64),
-        "ks_merge_parts": ([P, I64, I32, P, P], I32),
-        "ks_multi_last_stats": ([P, I32], I32),
-        "ks_region_spectra": ([P, P, P, I32, P, P, P, I64, I32, I32, P, P], I32),
-        "ks_region_spectra_dev": ([P, P, P, P, P, I64, I32, I32, P, P, P], I32),
-        "ks_spectra_tile_bases": ([], I32),
-        "ks_spectra_dist": ([P, P, I64, I32, P, I64, I32, P], I32),
-        "ks_spectra_dist_dev": ([P, P, I64, I32, P, I64, I32, P, P], I32),
-        "ks_spectra_cross_dist": ([P, P, I64, I32, P, I64, P, I64, I32, P], I32),
-        "ks_spectra_cross_dist_dev": ([P, P, I64, I32, P, I64, P, I64, I32, P, P], I32),
-        "ks_dist_pair_offsets": ([P, P, I64, I64, P], None),
-        "ks_dist_tiles_of": ([P, I64, I64, P, P], None),
-        "ks_dist_tile_rows": ([], I32),
-        "ks_hclust": ([P, P, I64, I32, P, P, P], I32),
-        "ks_hclust_dev": ([P, P, I64, I32, I32, P, P, P, P], I32),
-        "ks_hclust_cut": ([P, P, I64, I32, D, P], I32),
-        "ks_nj": ([P, P, I64, P, P, P, P], I32),
-        "ks_nj_dev": ([P, P, I64, I32, P, P, P, P, P], I32),
-        "ks_nj_edges": ([P, P, P, P, I64, P, P], I32),
-        "ks_silhouette": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P], I32),
-        "ks_silhouette_dev": ([P, P, I64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P], I32),
-        "ks_spectra_pca": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P], I32),
-        "ks_spectra_pca_dev": ([P, P, I64, I32, P, I64, I32, I32, P, P, P, P, P, P], I32),
-        "ks_pca_round_pairs": ([I32, I32, P, P], I32),
-        "ks_spectra_kmeans": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P], I32),
-        "ks_spectra_kmeans_dev": ([P, P, I64, I32, P, I64, P, P, I32, I32, I32, P, P, P, P, P, P], I32),
-        "ks_spectra_group_means": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P], I32),
-        "ks_spectra_group_means_dev": ([P, P, I64, I32, P, I64, P, I32, I32, P, P, P, P], I32),
-        "ks_spectra_kmeans_seed": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P], I32),
-        "ks_spectra_kmeans_seed_dev": ([P, P, I64, I32, P, I64, I32, I32, I64, P, P, P, P, P, P, P, P], I32),
-        "ks_spectra_knn": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P], I32),
-        "ks_spectra_knn_dev": ([P, P, I64, I32, P, I64, P, I64, I32, I32, P, P, P], I32),
-        "ks_seq_index_create": ([P, P], I32),
-        "ks_seq_index_destroy": ([P], None),
-        "ks_seq_index_info_get": ([P, P], I32),
-        "ks_scan_dev_indexed": ([P, P, P, I32, P, I32, D, P, P, P], I32),
-        "ks_tr_lr_dev_indexed": ([P, P, P, I32, P, P, I32, P, P], I32),
-        "ks_scan_chunk_indices": ([], I32),
-        "ks_scan_tile_chunks": ([], I32),
-    }
-    for name, (args, res) in sigs.items():
-        f = getattr(L, name)
-        f.argtypes = args
-        f.restype = res
+    _type_library(L)
     _lib = L
     return L
 
@@ -411,7 +369,11 @@ def shard_plan(seqs, nparts: int):
 
 
 def multi_last_stats():
-    """Phases of the last multi-device host call (ks_multi_last_stats, ms)."""
+    """Phases of the last multi-device host call (ks_multi_last_stats, ms).
+    host_sum_ms is the sum of the parts' histograms: on the host for
+    kmer_counts and kmer_regions, but for kmer_low_comp_regions the count sum
+    on the devices (reduce-scatter and all-gather of stripes); the key keeps
+    its name."""
     L = load()
     n = L.ks_multi_last_stats(None, 0)
     v = (C.c_double * n)()
@@ -467,13 +429,54 @@ def context(device: int = 0) -> Context:
     return ctx
 
 
-def hclust_n(length: int) -> int:
-    """n of a condensed vector of n(n-1)/2 entries (n >= 2), or an error."""
+def host_ptr(a):
+    """The address of an optional numpy array (None stays None, the C NULL)."""
+    return None if a is None else a.ctypes.data
+
+
+def counts_arg(counts):
+    """(contiguous uint32 [n, ncol], n, ncol) of a counts matrix, or an error."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.dtype.kind not in "iu":
+        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
+    if c.dtype != np.uint32:
+        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+            raise KmerSpansError("counts must be in the uint32 range")
+        c = c.astype(np.uint32)
+    return np.ascontiguousarray(c), int(c.shape[0]), int(c.shape[1])
+
+
+def rows_arg(rows, what: str, n: int):
+    """(int64 row indices or None, rows selected) of a row selection: None
+    selects n rows (the library reads that as rows 0 .. n - 1)."""
+    if rows is None:
+        return None, n
+    r = np.asarray(rows)
+    if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
+        raise KmerSpansError(f"{what} must be a 1-d array of integer row indices")
+    return np.ascontiguousarray(r, dtype=np.int64), int(r.size)
+
+
+def condensed_n(length: int, least: int) -> int:
+    """n of a condensed vector of n(n-1)/2 entries (n >= least), or an error."""
     n = (1 + int(np.sqrt(1.0 + 8.0 * length))) // 2
     for m in (n - 1, n, n + 1):
-        if m >= 2 and m * (m - 1) // 2 == length:
+        if m >= least and m * (m - 1) // 2 == length:
             return m
-    raise KmerSpansError(f"a condensed vector holds n(n-1)/2 entries for some n >= 2; {length} is no such number")
+    raise KmerSpansError(f"a condensed vector holds n(n-1)/2 entries for some n >= {least}; {length} is no such "
+                         "number")
+
+
+def condensed_arg(dist, least: int):
+    """(float64 condensed vector, its n >= least) of a dist argument."""
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    if d.ndim != 1:
+        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
+    return d, condensed_n(int(d.size), least)
+
+
+def hclust_n(length: int) -> int:
+    return condensed_n(length, 2)
 
 
 def hclust_method(method) -> int:
@@ -487,12 +490,7 @@ def hclust_outputs(n: int):
 
 
 def nj_n(length: int) -> int:
-    """n of a condensed vector of n(n-1)/2 entries (n >= 3), or an error."""
-    n = (1 + int(np.sqrt(1.0 + 8.0 * length))) // 2
-    for m in (n - 1, n, n + 1):
-        if m >= 3 and m * (m - 1) // 2 == length:
-            return m
-    raise KmerSpansError(f"a condensed vector holds n(n-1)/2 entries for some n >= 3; {length} is no such number")
+    return condensed_n(length, 3)
 
 
 def nj_outputs(n: int):

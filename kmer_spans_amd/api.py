@@ -29,7 +29,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import KmerSpansError, Regions, check, load, regions_to_numpy
+from ._lib import KmerSpansError, Regions, check, host_ptr, load, regions_to_numpy
 
 
 class _HostSeqs:
@@ -136,8 +136,7 @@ def kmer_regions(seq, k: int, kmer_scores, min_width: int, min_score: float, vis
     n = C.c_double(0)
     r = Regions()
     check(load().ks_kmer_regions(_ctx(device), hs.ptrs, hs.lens.ctypes.data, hs.n, k, w.ctypes.data,
-                                 w.size, int(min_width), float(min_score),
-                                 vis.ctypes.data if vis is not None else None, C.byref(n), C.byref(r)))
+                                 w.size, int(min_width), float(min_score), host_ptr(vis), C.byref(n), C.byref(r)))
     pos, score = regions_to_numpy(r)
     return {"n": n.value, "counts": vis, "pos": pos, "score": score}
 
@@ -234,15 +233,6 @@ def region_spectra(seq, pos, q: int = 4, both_strands: bool = True, seq_base: in
     return {"kmers": kmer_seq(q), "counts": counts, "freq": freq, "entropy": ent}
 
 
-def _rows_arg(rows, what):
-    if rows is None:
-        return None
-    r = np.asarray(rows)
-    if r.ndim != 1 or (r.size and r.dtype.kind not in "iu"):
-        raise KmerSpansError(f"{what} must be a 1-d array of integer row indices")
-    return np.ascontiguousarray(r, dtype=np.int64)
-
-
 def region_distances(counts, rows=None, rows_b=None, squared: bool = False, device: int = 0) -> np.ndarray:
     """Euclidean distances between row-normalised spectra (R's dist() on
     reg.kmer.sp, test.R:762-807) from the counts region_spectra returns.
@@ -257,28 +247,18 @@ def region_distances(counts, rows=None, rows_b=None, squared: bool = False, devi
     of the selected rows (all rows when rows is None) in the order of R's dist
     object and scipy's pdist.  Otherwise the dense float64[na, nb] block of
     rows (all rows when None) against rows_b."""
-    c = np.asarray(counts)
-    if c.ndim != 2 or c.dtype.kind not in "iu":
-        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
-    if c.dtype != np.uint32:
-        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
-            raise KmerSpansError("counts must be in the uint32 range")
-        c = c.astype(np.uint32)
-    c = np.ascontiguousarray(c)
-    n, ncol = (int(x) for x in c.shape)
-    ra, rb = _rows_arg(rows, "rows"), _rows_arg(rows_b, "rows_b")
-    na = n if ra is None else int(ra.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    ra, na = _lib.rows_arg(rows, "rows", n)
+    rb, nb = _lib.rows_arg(rows_b, "rows_b", 0)
     flags = _lib.KS_DIST_SQUARED if squared else 0
     L = load()
     if rows_b is None:
         out = np.zeros(na * (na - 1) // 2 if na > 1 else 0, dtype=np.float64)
-        check(L.ks_spectra_dist(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None,
-                                na, flags, out.ctypes.data))
+        check(L.ks_spectra_dist(_ctx(device), c.ctypes.data, n, ncol, host_ptr(ra), na, flags, out.ctypes.data))
         return out
-    nb = int(rb.size)
     out = np.zeros((na, nb), dtype=np.float64)
-    check(L.ks_spectra_cross_dist(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None,
-                                  na, rb.ctypes.data, nb, flags, out.ctypes.data))
+    check(L.ks_spectra_cross_dist(_ctx(device), c.ctypes.data, n, ncol, host_ptr(ra), na, rb.ctypes.data, nb, flags,
+                                  out.ctypes.data))
     return out
 
 
@@ -298,37 +278,17 @@ def region_pca(counts, rows=None, center: bool = True, ncomp=None, scores: bool 
     centred), 'x': float64[m, ncomp] scores, or None with scores=False}.  The
     centre and the scores are fixed orders of FP64 operations
     (include/kmer_spans.h); the same input gives the same bits on every run."""
-    c = np.asarray(counts)
-    if c.ndim != 2 or c.dtype.kind not in "iu":
-        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
-    if c.dtype != np.uint32:
-        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
-            raise KmerSpansError("counts must be in the uint32 range")
-        c = c.astype(np.uint32)
-    c = np.ascontiguousarray(c)
-    n, ncol = (int(v) for v in c.shape)
-    r = _rows_arg(rows, "rows")
-    m = n if r is None else int(r.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    r, m = _lib.rows_arg(rows, "rows", n)
     k = ncol if ncomp is None else int(ncomp)
     kk = max(0, min(k, ncol))  # a bad ncomp is the library's error; the buffers only need a size
     cen, sdev = np.zeros(ncol, dtype=np.float64), np.zeros(ncol, dtype=np.float64)
     rot = np.zeros((ncol, kk), dtype=np.float64)
     x = np.zeros((max(m, 0), kk), dtype=np.float64) if scores else None
-    check(load().ks_spectra_pca(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None, m,
+    check(load().ks_spectra_pca(_ctx(device), c.ctypes.data, n, ncol, host_ptr(r), m,
                                 0 if center else _lib.KS_PCA_NO_CENTER, k, cen.ctypes.data, sdev.ctypes.data,
-                                rot.ctypes.data, x.ctypes.data if x is not None else None, None))
+                                rot.ctypes.data, host_ptr(x), None))
     return {"sdev": sdev, "rotation": rot, "center": cen, "x": x}
-
-
-def _counts_arg(counts):
-    c = np.asarray(counts)
-    if c.ndim != 2 or c.dtype.kind not in "iu":
-        raise KmerSpansError("counts must be a [n, ncol] matrix of integer counts")
-    if c.dtype != np.uint32:
-        if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
-            raise KmerSpansError("counts must be in the uint32 range")
-        c = c.astype(np.uint32)
-    return np.ascontiguousarray(c)
 
 
 def region_kmeans(counts, centers, rows=None, iter_max: int = 10, device: int = 0) -> dict:
@@ -352,20 +312,16 @@ def region_kmeans(counts, centers, rows=None, iter_max: int = 10, device: int = 
     are one update ahead of the labels.  Every sum is a fixed order of FP64
     operations (include/kmer_spans.h): the same input gives the same bits on
     every run."""
-    c = _counts_arg(counts)
-    n, ncol = (int(v) for v in c.shape)
-    r = _rows_arg(rows, "rows")
-    m = n if r is None else int(r.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    r, m = _lib.rows_arg(rows, "rows", n)
     init, init_rows, g = _lib.kmeans_centers(centers, ncol)
     cluster = np.zeros(max(m, 0), dtype=np.int32)
     cen = np.zeros((g, ncol), dtype=np.float64)
     size, wss = np.zeros(g, dtype=np.int32), np.zeros(g, dtype=np.float64)
     res = _lib.KmeansResult()
-    check(load().ks_spectra_kmeans(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None, m,
-                                   init.ctypes.data if init is not None else None,
-                                   init_rows.ctypes.data if init_rows is not None else None, g, int(iter_max), 0,
-                                   cluster.ctypes.data, cen.ctypes.data, size.ctypes.data, wss.ctypes.data,
-                                   C.byref(res)))
+    check(load().ks_spectra_kmeans(_ctx(device), c.ctypes.data, n, ncol, host_ptr(r), m, host_ptr(init),
+                                   host_ptr(init_rows), g, int(iter_max), 0, cluster.ctypes.data, cen.ctypes.data,
+                                   size.ctypes.data, wss.ctypes.data, C.byref(res)))
     return dict({"cluster": cluster, "centers": cen, "size": size, "withinss": wss}, **_lib.kmeans_result(res))
 
 
@@ -380,16 +336,14 @@ def region_group_means(counts, group, ngroups=None, rows=None, device: int = 0) 
     {'centers': float64[g, ncol] (a row of NaN for a group without members),
     'size': int32[g], 'withinss': float64[g] (0 for an empty group)}.  The
     centres can start region_kmeans when no group is empty."""
-    c = _counts_arg(counts)
-    n, ncol = (int(v) for v in c.shape)
-    r = _rows_arg(rows, "rows")
-    m = n if r is None else int(r.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    r, m = _lib.rows_arg(rows, "rows", n)
     g, ng = _lib.silhouette_group(group, m, ngroups)
     ngb = min(ng, _lib.KS_KM_MAX_GROUPS)  # a larger ngroups is the library's error; the buffers only need a size
     cen = np.zeros((ngb, ncol), dtype=np.float64)
     size, wss = np.zeros(ngb, dtype=np.int32), np.zeros(ngb, dtype=np.float64)
-    check(load().ks_spectra_group_means(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None,
-                                        m, g.ctypes.data, ng, 0, cen.ctypes.data, size.ctypes.data, wss.ctypes.data))
+    check(load().ks_spectra_group_means(_ctx(device), c.ctypes.data, n, ncol, host_ptr(r), m, g.ctypes.data, ng, 0,
+                                        cen.ctypes.data, size.ctypes.data, wss.ctypes.data))
     return {"centers": cen, "size": size, "withinss": wss}
 
 
@@ -420,19 +374,16 @@ def region_kmeans_seed(counts, g, method: str = "maximin", rows=None, first=0, u
     after the last pick and its row}.  Every value is a fixed order of FP64
     operations (include/kmer_spans.h): the same input gives the same bits on
     every run."""
-    c = _counts_arg(counts)
-    n, ncol = (int(v) for v in c.shape)
-    r = _rows_arg(rows, "rows")
-    m = n if r is None else int(r.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    r, m = _lib.rows_arg(rows, "rows", n)
     g, gb, flags, first, u = _lib.seed_args(g, method, first, u, seed)
     picked = np.zeros(gb, dtype=np.int64)
     near, mind = np.zeros(max(m, 0), dtype=np.int32), np.zeros(max(m, 0), dtype=np.float64)
     pd, pot = np.zeros(gb, dtype=np.float64), np.zeros(gb, dtype=np.float64)
     res = _lib.SeedResult()
-    check(load().ks_spectra_kmeans_seed(_ctx(device), c.ctypes.data, n, ncol, r.ctypes.data if r is not None else None,
-                                        m, g, flags, first, u.ctypes.data if u is not None else None,
-                                        picked.ctypes.data, near.ctypes.data, mind.ctypes.data, pd.ctypes.data,
-                                        pot.ctypes.data, C.byref(res)))
+    check(load().ks_spectra_kmeans_seed(_ctx(device), c.ctypes.data, n, ncol, host_ptr(r), m, g, flags, first,
+                                        host_ptr(u), picked.ctypes.data, near.ctypes.data, mind.ctypes.data,
+                                        pd.ctypes.data, pot.ctypes.data, C.byref(res)))
     return dict({"rows": picked, "nearest": near, "mindist": mind, "pick_dist": pd, "potential": pot},
                 **_lib.seed_result(res))
 
@@ -456,16 +407,13 @@ def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device:
     float64 [na, k], column 0 the nearest; the k candidates with the smallest
     (squared distance, position), ascending, so ties go to the lowest position
     and the same input gives the same bits on every run."""
-    c = _counts_arg(counts)
-    n, ncol = (int(v) for v in c.shape)
-    ra, rb = _rows_arg(rows, "rows"), _rows_arg(rows_b, "rows_b")
-    na = n if ra is None else int(ra.size)
-    nb = 0 if rb is None else int(rb.size)
+    c, n, ncol = _lib.counts_arg(counts)
+    ra, na = _lib.rows_arg(rows, "rows", n)
+    rb, nb = _lib.rows_arg(rows_b, "rows_b", 0)
     k, kb = _lib.knn_k(k)
     index = np.zeros((max(na, 0), kb), dtype=np.int64)
     dist = np.zeros((max(na, 0), kb), dtype=np.float64)
-    check(load().ks_spectra_knn(_ctx(device), c.ctypes.data, n, ncol, ra.ctypes.data if ra is not None else None, na,
-                                rb.ctypes.data if rb is not None else None, nb, k,
+    check(load().ks_spectra_knn(_ctx(device), c.ctypes.data, n, ncol, host_ptr(ra), na, host_ptr(rb), nb, k,
                                 _lib.KS_DIST_SQUARED if squared else 0, index.ctypes.data, dist.ctypes.data))
     return index, dist
 
@@ -483,10 +431,7 @@ def region_hclust(dist, method: str = "complete", device: int = 0) -> dict:
     float64[n-1], 'order': int32[n], 'method'} as in R's hclust object:
     observation i (0-based) is -(i+1), the cluster of step t is t+1, order
     lists the leaves 1-based from left to right."""
-    d = np.ascontiguousarray(dist, dtype=np.float64)
-    if d.ndim != 1:
-        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
-    n = _lib.hclust_n(int(d.size))
+    d, n = _lib.condensed_arg(dist, 2)
     merge, height, order = _lib.hclust_outputs(n)
     check(load().ks_hclust(_ctx(device), d.ctypes.data, n, _lib.hclust_method(method), merge.ctypes.data,
                            height.ctypes.data, order.ctypes.data))
@@ -541,10 +486,7 @@ def region_nj(dist, device: int = 0) -> dict:
     length[t] into node t+1, observation i (0-based) is -(i+1), and root names
     the three children of the final trifurcation.  Negative lengths are
     returned as computed."""
-    d = np.ascontiguousarray(dist, dtype=np.float64)
-    if d.ndim != 1:
-        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
-    n = _lib.nj_n(int(d.size))
+    d, n = _lib.condensed_arg(dist, 3)
     join, length, root, root_length = _lib.nj_outputs(n)
     check(load().ks_nj(_ctx(device), d.ctypes.data, n, join.ctypes.data, length.ctypes.data, root.ctypes.data,
                        root_length.ctypes.data))
@@ -569,15 +511,12 @@ def region_silhouette(dist, group, ngroups=None, sums: bool = False, device: int
     sums=True also 'sums': float64[n, g], the sum of D(i, j) over the members j
     of each group.  Every sum is a fixed order of FP64 additions
     (include/kmer_spans.h): the same input gives the same bits on every run."""
-    d = np.ascontiguousarray(dist, dtype=np.float64)
-    if d.ndim != 1:
-        raise KmerSpansError("dist must be a 1-d condensed dissimilarity vector")
-    n = _lib.hclust_n(int(d.size))
+    d, n = _lib.condensed_arg(dist, 2)
     g, ng = _lib.silhouette_group(group, n, ngroups)
     res = _lib.silhouette_outputs(n, ng)
     s = np.zeros((n, ng), dtype=np.float64) if sums else None
     check(load().ks_silhouette(_ctx(device), d.ctypes.data, n, g.ctypes.data, ng, 0, *_lib.silhouette_out_args(res),
-                               s.ctypes.data if s is not None else None))
+                               host_ptr(s)))
     res["avg_width_all"] = float(res["avg_width_all"][0])
     if sums:
         res["sums"] = s
@@ -769,7 +708,7 @@ def window_kmer_dist(seq, kmers, window: int, freq: bool = True, ret_flag: int =
     sp = None
     if ret_flag & 1:
         scores = [np.zeros((n, int(L)), dtype=np.int32) if L > window else None for L in hs.lens[:hs.n]]
-        sp = (C.c_void_p * max(hs.n, 1))(*[s.ctypes.data if s is not None else None for s in scores])
+        sp = (C.c_void_p * max(hs.n, 1))(*[host_ptr(s) for s in scores])
     check(load().ks_windowed_dist(_ctx(device), hs.ptrs, hs.lens.ctypes.data, hs.n, kp, n, k, window,
                                   int(ret_flag), dist.ctypes.data, inc.ctypes.data, sp))
     d = dist.T.copy()

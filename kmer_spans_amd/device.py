@@ -46,12 +46,8 @@ class SeqIndex:
         """Scans that started pass 1 from the previous scan's exact chunk entries
         and verified them (entry_reuses), and calls whose verification failed
         and that were rerun on the hint path (entry_fallbacks)."""
-        # (typed here, not in _lib.load(): KS_LIB_PATH may name an earlier build, for A/B runs, without it)
-        fn = load().ks_seq_index_entry_info
-        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        fn.restype = C.c_int32
         r, f = C.c_int64(), C.c_int64()
-        check(fn(self._h, C.byref(r), C.byref(f)))
+        check(load().ks_seq_index_entry_info(self._h, C.byref(r), C.byref(f)))
         return {"entry_reuses": int(r.value), "entry_fallbacks": int(f.value)}
 
     def codes_info(self) -> dict:
@@ -59,11 +55,8 @@ class SeqIndex:
         that streamed them instead of reading table lines (code_reuses), reading
         calls rerun on the hint path (code_fallbacks) and calls that went
         without the slot for want of memory (code_alloc_failures)."""
-        fn = load().ks_seq_index_codes_info
-        fn.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
-        fn.restype = C.c_int32
         v = [C.c_int64() for _ in range(4)]
-        check(fn(self._h, *[C.byref(x) for x in v]))
+        check(load().ks_seq_index_codes_info(self._h, *[C.byref(x) for x in v]))
         names = ("code_builds", "code_reuses", "code_fallbacks", "code_alloc_failures")
         return {n: int(x.value) for n, x in zip(names, v)}
 
@@ -293,11 +286,8 @@ class DeviceTable:
 def kept_codes_layout(J: int, nch: int, c: int, i: int) -> tuple[int, int]:
     """ks_kept_codes_layout: (bytes of the kept codes of nch chunks in steps of
     J, halfword offset of scan index i of chunk c).  Host arithmetic only."""
-    fn = load().ks_kept_codes_layout
-    fn.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    fn.restype = C.c_int32
     b, h = C.c_int64(), C.c_int64()
-    check(fn(int(J), int(nch), int(c), int(i), C.byref(b), C.byref(h)))
+    check(load().ks_kept_codes_layout(int(J), int(nch), int(c), int(i), C.byref(b), C.byref(h)))
     return int(b.value), int(h.value)
 
 
@@ -305,13 +295,20 @@ def kept_codes_read(ctx: _lib.Context, c0: int, nchunks: int) -> tuple[np.ndarra
     """ks_kept_codes_debug_read: the kept codes of chunks [c0, c0 + nchunks) of
     ctx's last chunked scan as uint16 [nchunks, 256] in index order, and the
     step J they were written in (tests)."""
-    fn = load().ks_kept_codes_debug_read
-    fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int32)]
-    fn.restype = C.c_int32
     out = np.zeros((int(nchunks), 256), dtype=np.uint16)
     j = C.c_int32()
-    check(fn(ctx.handle if ctx is not None else None, int(c0), int(nchunks), out.ctypes.data, C.byref(j)))
+    check(load().ks_kept_codes_debug_read(_handle(ctx), int(c0), int(nchunks), out.ctypes.data, C.byref(j)))
     return out, int(j.value)
+
+
+def _handle(ctx):
+    """The ks_ctx of a Context; None is the library's default context on device 0."""
+    return None if ctx is None else ctx.handle
+
+
+def _ptr(t):
+    """The device address of an optional tensor (None and an empty one are the C NULL)."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 def bind_torch_stream(ctx: _lib.Context) -> None:
@@ -435,8 +432,7 @@ class FastaSeqs:
 def load_fasta(ctx: _lib.Context | None, path: str, min_len: int = 0) -> FastaSeqs:
     """ks_fasta_load: plain or gzip FASTA -> device-resident records."""
     f = Fasta()
-    check(load().ks_fasta_load(ctx.handle if ctx is not None else None, str(path).encode(), int(min_len),
-                               C.byref(f)))
+    check(load().ks_fasta_load(_handle(ctx), str(path).encode(), int(min_len), C.byref(f)))
     return FastaSeqs(f)
 
 
@@ -444,7 +440,7 @@ def parse_fasta(ctx: _lib.Context | None, text, min_len: int = 0) -> FastaSeqs:
     """ks_fasta_parse: FASTA text (str/bytes) -> device-resident records."""
     b = text.encode("latin-1") if isinstance(text, str) else bytes(text)
     f = Fasta()
-    check(load().ks_fasta_parse(ctx.handle if ctx is not None else None, b, len(b), int(min_len), C.byref(f)))
+    check(load().ks_fasta_parse(_handle(ctx), b, len(b), int(min_len), C.byref(f)))
     return FastaSeqs(f)
 
 
@@ -524,27 +520,44 @@ def region_spectra(ctx: _lib.Context, ds, pos, q: int = 4, both_strands: bool = 
     st = SpectraStats()
     s = ds.struct()
     _order(ctx)
-    check(load().ks_region_spectra_dev(ctx.handle if ctx is not None else None, C.byref(s),
-                                       C.c_void_p(ids.data_ptr()), C.c_void_p(p[1].data_ptr()),
-                                       C.c_void_p(p[2].data_ptr()), n, q,
+    check(load().ks_region_spectra_dev(_handle(ctx), C.byref(s), C.c_void_p(ids.data_ptr()),
+                                       C.c_void_p(p[1].data_ptr()), C.c_void_p(p[2].data_ptr()), n, q,
                                        _lib.KS_SPECTRA_BOTH_STRANDS if both_strands else 0,
-                                       C.c_void_p(counts.data_ptr()),
-                                       C.c_void_p(ent.data_ptr()) if ent is not None else None, C.byref(st)))
+                                       C.c_void_p(counts.data_ptr()), _ptr(ent), C.byref(st)))
     return counts, ent, st.as_dict()
 
 
-def _rows_dev(rows, what, dev):
-    """A row selection as a contiguous int64 CUDA tensor (numpy is uploaded)."""
+def _counts_dev(counts):
+    """(device, n, ncol) of a counts tensor, which the library reads in place."""
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
+            or counts.dim() != 2 or not counts.is_contiguous()):
+        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
+    return counts.device, int(counts.shape[0]), int(counts.shape[1])
+
+
+def _rows_dev(rows, what, dev, n):
+    """(contiguous int64 CUDA tensor or None, rows selected) of a row
+    selection (numpy is uploaded): None selects n rows."""
+    if rows is None:
+        return None, n
     if isinstance(rows, torch.Tensor):
         if rows.dtype != torch.int64 or not rows.is_cuda or rows.dim() != 1:
             raise _lib.KmerSpansError(f"{what} must be a 1-d int64 array (numpy or cuda tensor)")
         if rows.device != dev:
             raise _lib.KmerSpansError(f"{what} is on {rows.device}, the counts are on {dev}")
-        return rows.contiguous()
+        return rows.contiguous(), int(rows.numel())
     a = np.asarray(rows)
     if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
         raise _lib.KmerSpansError(f"{what} must be a 1-d int64 array (numpy or cuda tensor)")
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev), int(a.size)
+
+
+def _dist_dev(dist, least):
+    """n >= least of a condensed distance tensor, which the library reads in place."""
+    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
+            or not dist.is_contiguous()):
+        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
+    return _lib.condensed_n(int(dist.numel()), least)
 
 
 def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=None, squared: bool = False,
@@ -561,18 +574,13 @@ def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=
     block of rows against rows_b.  squared=True skips the square root.  out=
     (float64 CUDA, contiguous, as many elements) is reused for the result.
     Returns (distances, stats dict of ks_dist_stats)."""
-    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
-            or counts.dim() != 2 or not counts.is_contiguous()):
-        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
-    dev = counts.device
-    n, ncol = int(counts.shape[0]), int(counts.shape[1])
-    ra = _rows_dev(rows, "rows", dev) if rows is not None else None
-    rb = _rows_dev(rows_b, "rows_b", dev) if rows_b is not None else None
-    na = n if ra is None else int(ra.numel())
+    dev, n, ncol = _counts_dev(counts)
+    ra, na = _rows_dev(rows, "rows", dev, n)
+    rb, nb = _rows_dev(rows_b, "rows_b", dev, 0)
     if rb is None:
         shape = (na * (na - 1) // 2 if na > 1 else 0,)
     else:
-        shape = (na, int(rb.numel()))
+        shape = (na, nb)
     numel = int(np.prod(shape, dtype=np.int64))
     if out is not None:
         if out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.numel() != numel:
@@ -584,15 +592,13 @@ def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=
         res = torch.empty(shape, dtype=torch.float64, device=dev)
     st = _lib.DistStats()
     flags = _lib.KS_DIST_SQUARED if squared else 0
-    h = ctx.handle if ctx is not None else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     _order(ctx)
     if rb is None:
-        check(load().ks_spectra_dist_dev(h, C.c_void_p(counts.data_ptr()), n, ncol, ptr(ra), na, flags, ptr(res),
-                                         C.byref(st)))
+        check(load().ks_spectra_dist_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(ra), na, flags,
+                                         _ptr(res), C.byref(st)))
     else:
-        check(load().ks_spectra_cross_dist_dev(h, C.c_void_p(counts.data_ptr()), n, ncol, ptr(ra), na, ptr(rb),
-                                               int(rb.numel()), flags, ptr(res), C.byref(st)))
+        check(load().ks_spectra_cross_dist_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(ra), na,
+                                               _ptr(rb), nb, flags, _ptr(res), C.byref(st)))
     return res, st.as_dict()
 
 
@@ -609,14 +615,11 @@ def region_hclust(ctx: _lib.Context, dist: torch.Tensor, method: str = "complete
     float64 [n-1], order int32 [n] (numpy, as R's hclust object: observation i
     is -(i+1), step t is t+1, order is 1-based) and method; stats the dict of
     ks_hclust_stats."""
-    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
-            or not dist.is_contiguous()):
-        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
-    n = _lib.hclust_n(int(dist.numel()))
+    n = _dist_dev(dist, 2)
     merge, height, order = _lib.hclust_outputs(n)
     st = _lib.HclustStats()
     _order(ctx)
-    check(load().ks_hclust_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n,
+    check(load().ks_hclust_dev(_handle(ctx), C.c_void_p(dist.data_ptr()), n,
                                _lib.hclust_method(method), _lib.KS_HCLUST_KEEP_INPUT if keep_input else 0,
                                merge.ctypes.data, height.ctypes.data, order.ctypes.data, C.byref(st)))
     return {"merge": merge, "height": height, "order": order, "method": method}, st.as_dict()
@@ -635,17 +638,13 @@ def region_nj(ctx: _lib.Context, dist: torch.Tensor, keep_input: bool = True, co
     join int32 [n-3, 2], length float64 [n-3, 2], root int32 [3] and
     root_length float64 [3] (numpy; observation i is -(i+1), the node of step t
     is t+1); stats the dict of ks_nj_stats."""
-    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
-            or not dist.is_contiguous()):
-        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
-    n = _lib.nj_n(int(dist.numel()))
+    n = _dist_dev(dist, 3)
     join, length, root, root_length = _lib.nj_outputs(n)
     st = _lib.NjStats()
     flags = (_lib.KS_NJ_KEEP_INPUT if keep_input else 0) | (0 if compact else _lib.KS_NJ_NO_COMPACT)
     _order(ctx)
-    check(load().ks_nj_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n, flags,
-                           join.ctypes.data, length.ctypes.data, root.ctypes.data, root_length.ctypes.data,
-                           C.byref(st)))
+    check(load().ks_nj_dev(_handle(ctx), C.c_void_p(dist.data_ptr()), n, flags, join.ctypes.data, length.ctypes.data,
+                           root.ctypes.data, root_length.ctypes.data, C.byref(st)))
     return {"join": join, "length": length, "root": root, "root_length": root_length}, st.as_dict()
 
 
@@ -666,10 +665,7 @@ def region_silhouette(ctx: _lib.Context, dist: torch.Tensor, group, ngroups=None
     'avg_width_all'; with sums=True also 'sums', a float64 CUDA tensor [n, g]
     of the group sums S(i, c) (include/kmer_spans.h has the order of every
     addition).  stats is the dict of ks_silhouette_stats."""
-    if (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or not dist.is_cuda or dist.dim() != 1
-            or not dist.is_contiguous()):
-        raise _lib.KmerSpansError("dist must be a contiguous 1-d float64 cuda tensor")
-    n = _lib.hclust_n(int(dist.numel()))
+    n = _dist_dev(dist, 2)
     if isinstance(group, torch.Tensor):
         group = group.detach().cpu().numpy()
     g, ng = _lib.silhouette_group(group, n, ngroups)
@@ -677,9 +673,8 @@ def region_silhouette(ctx: _lib.Context, dist: torch.Tensor, group, ngroups=None
     s = torch.empty((n, ng), dtype=torch.float64, device=dist.device) if sums else None
     st = _lib.SilhouetteStats()
     _order(ctx)
-    check(load().ks_silhouette_dev(ctx.handle if ctx is not None else None, C.c_void_p(dist.data_ptr()), n,
-                                   g.ctypes.data, ng, 0, *_lib.silhouette_out_args(res),
-                                   C.c_void_p(s.data_ptr()) if s is not None else None, C.byref(st)))
+    check(load().ks_silhouette_dev(_handle(ctx), C.c_void_p(dist.data_ptr()), n, g.ctypes.data, ng, 0,
+                                   *_lib.silhouette_out_args(res), _ptr(s), C.byref(st)))
     res["avg_width_all"] = float(res["avg_width_all"][0])
     if sums:
         res["sums"] = s
@@ -702,13 +697,8 @@ def region_pca(ctx: _lib.Context, counts: torch.Tensor, rows=None, center: bool 
     [m, ncomp] (None with scores=False) and, with gram=True, 'G' [ncol, ncol],
     the cross-product matrix of the (centred) profiles; stats the dict of
     ks_pca_stats."""
-    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
-            or counts.dim() != 2 or not counts.is_contiguous()):
-        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
-    dev = counts.device
-    n, ncol = int(counts.shape[0]), int(counts.shape[1])
-    r = _rows_dev(rows, "rows", dev) if rows is not None else None
-    m = n if r is None else int(r.numel())
+    dev, n, ncol = _counts_dev(counts)
+    r, m = _rows_dev(rows, "rows", dev, n)
     k = ncol if ncomp is None else int(ncomp)
     kk = max(0, min(k, ncol))  # a bad ncomp is the library's error; the buffers only need a size
     new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
@@ -716,20 +706,11 @@ def region_pca(ctx: _lib.Context, counts: torch.Tensor, rows=None, center: bool 
     if gram:
         res["G"] = new(ncol, ncol)
     st = _lib.PcaStats()
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     _order(ctx)
-    check(load().ks_spectra_pca_dev(ctx.handle, C.c_void_p(counts.data_ptr()), n, ncol,
-                                    ptr(r), m, 0 if center else _lib.KS_PCA_NO_CENTER, k, ptr(res["center"]),
-                                    ptr(res["sdev"]), ptr(res["rotation"]), ptr(res["x"]), ptr(res.get("G")),
-                                    C.byref(st)))
+    check(load().ks_spectra_pca_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(r), m,
+                                    0 if center else _lib.KS_PCA_NO_CENTER, k, _ptr(res["center"]), _ptr(res["sdev"]),
+                                    _ptr(res["rotation"]), _ptr(res["x"]), _ptr(res.get("G")), C.byref(st)))
     return res, st.as_dict()
-
-
-def _counts_dev(counts):
-    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda
-            or counts.dim() != 2 or not counts.is_contiguous()):
-        raise _lib.KmerSpansError("counts must be a contiguous int32 [n, ncol] cuda tensor")
-    return counts.device, int(counts.shape[0]), int(counts.shape[1])
 
 
 def region_kmeans(ctx: _lib.Context, counts: torch.Tensor, centers, rows=None, iter_max: int = 10):
@@ -752,8 +733,7 @@ def region_kmeans(ctx: _lib.Context, counts: torch.Tensor, centers, rows=None, i
     of ks_kmeans_stats.  include/kmer_spans.h has the order of every
     operation; one 4-byte read-back per pass is the only host round trip."""
     dev, n, ncol = _counts_dev(counts)
-    r = _rows_dev(rows, "rows", dev) if rows is not None else None
-    m = n if r is None else int(r.numel())
+    r, m = _rows_dev(rows, "rows", dev, n)
     init = init_rows = None
     if isinstance(centers, torch.Tensor) and centers.dim() == 2:
         if centers.dtype != torch.float64 or centers.shape[1] != ncol or not centers.shape[0]:
@@ -761,8 +741,7 @@ def region_kmeans(ctx: _lib.Context, counts: torch.Tensor, centers, rows=None, i
         init = centers.to(dev).contiguous()
         g = int(init.shape[0])
     elif isinstance(centers, torch.Tensor):
-        init_rows = _rows_dev(centers, "centers", dev)
-        g = int(init_rows.numel())
+        init_rows, g = _rows_dev(centers, "centers", dev, 0)
         if not g:
             raise _lib.KmerSpansError("centers names no row")
     else:
@@ -775,11 +754,10 @@ def region_kmeans(ctx: _lib.Context, counts: torch.Tensor, centers, rows=None, i
     cen = torch.empty((g, ncol), dtype=torch.float64, device=dev)
     size, wss = np.zeros(g, dtype=np.int32), np.zeros(g, dtype=np.float64)
     out, st = _lib.KmeansResult(), _lib.KmeansStats()
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     _order(ctx)
-    check(load().ks_spectra_kmeans_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n, ncol,
-                                       ptr(r), m, ptr(init), ptr(init_rows), g, int(iter_max), 0, ptr(cluster),
-                                       ptr(cen), size.ctypes.data, wss.ctypes.data, C.byref(out), C.byref(st)))
+    check(load().ks_spectra_kmeans_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(r), m, _ptr(init),
+                                       _ptr(init_rows), g, int(iter_max), 0, _ptr(cluster), _ptr(cen),
+                                       size.ctypes.data, wss.ctypes.data, C.byref(out), C.byref(st)))
     res = dict({"cluster": cluster, "centers": cen, "size": size, "withinss": wss}, **_lib.kmeans_result(out))
     return res, st.as_dict()
 
@@ -798,8 +776,7 @@ def region_group_means(ctx: _lib.Context, counts: torch.Tensor, group, ngroups=N
     'size' (int32 numpy [g]) and 'withinss' (float64 numpy [g]); stats the dict
     of ks_kmeans_stats."""
     dev, n, ncol = _counts_dev(counts)
-    r = _rows_dev(rows, "rows", dev) if rows is not None else None
-    m = n if r is None else int(r.numel())
+    r, m = _rows_dev(rows, "rows", dev, n)
     if isinstance(group, torch.Tensor):
         group = group.detach().cpu().numpy()
     g, ng = _lib.silhouette_group(group, m, ngroups)
@@ -808,9 +785,8 @@ def region_group_means(ctx: _lib.Context, counts: torch.Tensor, group, ngroups=N
     size, wss = np.zeros(ngb, dtype=np.int32), np.zeros(ngb, dtype=np.float64)
     st = _lib.KmeansStats()
     _order(ctx)
-    check(load().ks_spectra_group_means_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n,
-                                            ncol, C.c_void_p(r.data_ptr()) if r is not None and r.numel() else None,
-                                            m, g.ctypes.data, ng, 0, C.c_void_p(cen.data_ptr()), size.ctypes.data,
+    check(load().ks_spectra_group_means_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(r), m,
+                                            g.ctypes.data, ng, 0, C.c_void_p(cen.data_ptr()), size.ctypes.data,
                                             wss.ctypes.data, C.byref(st)))
     return {"centers": cen, "size": size, "withinss": wss}, st.as_dict()
 
@@ -832,20 +808,17 @@ def region_kmeans_seed(ctx: _lib.Context, counts: torch.Tensor, g, method: str =
     'n_distinct', 'potential_final', 'radius', 'far_row'; stats the dict of
     ks_seed_stats.  The g steps are queued without a host round trip."""
     dev, n, ncol = _counts_dev(counts)
-    r = _rows_dev(rows, "rows", dev) if rows is not None else None
-    m = n if r is None else int(r.numel())
+    r, m = _rows_dev(rows, "rows", dev, n)
     g, gb, flags, first, u = _lib.seed_args(g, method, first, u, seed)
     picked = torch.empty(gb, dtype=torch.int64, device=dev)
     near = torch.empty(m, dtype=torch.int32, device=dev)
     mind = torch.empty(m, dtype=torch.float64, device=dev)
     pd, pot = np.zeros(gb, dtype=np.float64), np.zeros(gb, dtype=np.float64)
     out, st = _lib.SeedResult(), _lib.SeedStats()
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     _order(ctx)
-    check(load().ks_spectra_kmeans_seed_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n,
-                                            ncol, ptr(r), m, g, flags, first, u.ctypes.data if u is not None else None,
-                                            ptr(picked), ptr(near), ptr(mind), pd.ctypes.data, pot.ctypes.data,
-                                            C.byref(out), C.byref(st)))
+    check(load().ks_spectra_kmeans_seed_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(r), m, g, flags,
+                                            first, _lib.host_ptr(u), _ptr(picked), _ptr(near), _ptr(mind),
+                                            pd.ctypes.data, pot.ctypes.data, C.byref(out), C.byref(st)))
     res = dict({"rows": picked, "nearest": near, "mindist": mind, "pick_dist": pd, "potential": pot},
                **_lib.seed_result(out))
     return res, st.as_dict()
@@ -870,19 +843,16 @@ def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=Non
     nearest, ordered by (squared distance, position); stats the dict of
     ks_knn_stats."""
     dev, n, ncol = _counts_dev(counts)
-    ra = _rows_dev(rows, "rows", dev) if rows is not None else None
-    rb = _rows_dev(rows_b, "rows_b", dev) if rows_b is not None else None
-    if rb is not None and not rb.numel():
+    ra, na = _rows_dev(rows, "rows", dev, n)
+    rb, nb = _rows_dev(rows_b, "rows_b", dev, 0)
+    if rb is not None and not nb:
         raise _lib.KmerSpansError("rows_b names no row")
-    na = n if ra is None else int(ra.numel())
-    nb = 0 if rb is None else int(rb.numel())
     k, kb = _lib.knn_k(k)
     index = torch.empty((na, kb), dtype=torch.int64, device=dev)
     dist = torch.empty((na, kb), dtype=torch.float64, device=dev)
     st = _lib.KnnStats()
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     _order(ctx)
-    check(load().ks_spectra_knn_dev(ctx.handle if ctx is not None else None, C.c_void_p(counts.data_ptr()), n, ncol,
-                                    ptr(ra), na, ptr(rb), nb, k, _lib.KS_DIST_SQUARED if squared else 0,
-                                    C.c_void_p(index.data_ptr()), C.c_void_p(dist.data_ptr()), C.byref(st)))
+    check(load().ks_spectra_knn_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(ra), na, _ptr(rb), nb,
+                                    k, _lib.KS_DIST_SQUARED if squared else 0, C.c_void_p(index.data_ptr()),
+                                    C.c_void_p(dist.data_ptr()), C.byref(st)))
     return index, dist, st.as_dict()
