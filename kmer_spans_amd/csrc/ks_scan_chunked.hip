@@ -852,15 +852,18 @@ __global__ void __launch_bounds__(1024) k_predict(Chunks g, int64_t total, int k
 // Every pass-1 kernel does the same work per scan index of a chunk and differs
 // only in how it fetches the value s: that work is P1Lane below (init / step /
 // finish), used by k_pass1l, k_pass1w, k_pass1r, k_pass1pf and k_pass1_lds.
-// Three kernels keep a walk of their own.  k_pass1_lds_int walks on int32:
+// Four kernels keep a walk of their own.  k_pass1_lds_int walks on int32:
 // 32-bit integer compares instead of FP64 ones are the point of that kernel.
 // k_pass1p keeps a copy in locals, for its registers (see there).  k_pass1
 // keeps its if / else-if form that asks decide(): on the walker its J = 1
 // instantiations took 147-161 VGPRs instead of 181-191 and ran slower (see
-// there).  All share the candidate append (cand_put) and the result store
-// (p1_put).  So the emission rule (the candidate test) is written in four
-// places: P1Lane::step, k_pass1p, for kmer_regions alone k_pass1_lds_int, and
-// decide(), which k_pass1 (cand_wanted), the stitch and k_candidates ask.
+// there).  k_pass1c without the visit histogram walks with code_index, the
+// exact-entry step arranged for a wave of full chunks (see there; its visit
+// flavour uses P1Lane).  All share the candidate append (cand_put) and the
+// result store (p1_put / finish_exact).  So the emission rule (the candidate
+// test) is written in five places: P1Lane::step, k_pass1p, code_index, for
+// kmer_regions alone k_pass1_lds_int, and decide(), which k_pass1
+// (cand_wanted), the stitch and k_candidates ask.
 
 // A closed candidate excursion of the chunk starting at scan index start
 // (chunk-relative beg, arg, end) joins the segmented list.
@@ -1999,10 +2002,16 @@ __global__ void __launch_bounds__(kWideBlock) k_pass1w(Chunks g, int64_t total, 
 // the table's -- finish_exact still verifies every exact entry bit for bit
 // (bit 64), which catches a wrong code wherever the carried sum does not clamp
 // -- not a proof.
-constexpr int kCodeBlock = 1024;
-// steps per batch; one batch is loaded while the one before is walked.  2: at
-// most 64 VGPRs without the visit walk, so two 1024-lane blocks share a CU (8
-// waves per SIMD, 48 KB of records in flight per CU); 4 took 68-76.
+// Lanes per block.  The LUT copy (up to 56 KB of the CU's 160 KB of LDS) lets
+// two blocks share a CU, whatever their size, so a CU holds 2 x kCodeBlock / 256
+// waves per SIMD if the registers allow.  The walk without the visit histogram
+// takes 64-82 VGPRs (7-6 waves per SIMD by registers): two 768-lane blocks are 6
+// waves per SIMD up to 85 VGPRs, where 1024-lane blocks would leave one block
+// (4 waves) on the CU from 65 VGPRs on.  The visit flavours take 78-88 VGPRs,
+// one block per CU either way: 1024 lanes keep their 4 waves per SIMD.
+constexpr int code_block(bool visits) { return visits ? 1024 : 768; }
+// steps per batch; one batch is loaded while the one before is walked (2: 36 KB
+// of records in flight per CU; 3 and 4 took 8-16 more VGPRs and gained nothing).
 constexpr int kCodeDepth = 2;
 
 // The k-mer (k <= 15) of bases [p0, p0 + k) from the packed words.
@@ -2013,26 +2022,106 @@ __device__ __forceinline__ uint32_t packed_kmer(const uint32_t *__restrict__ pac
   return (uint32_t)(x >> (64 - 2 * (sk + k))) & ((1u << (2 * k)) - 1u);
 }
 
+// One scan index of the reader's walk: P1Lane::step's exact-entry arithmetic on
+// the lane's state L -- the same FP64 operations in the same order -- less the
+// work whose outcome the wave already knows.  pos is prev > 0 carried from the
+// index before (prev is never NaN and never below 0, so prev == 0 is !pos and
+// S == 0 is !(S > 0)): open and close are two mask operations.  beg is not
+// reset at a close: it is read only while prev > 0, where it is the last open's
+// index, and finish_exact writes -1 for prev == 0 itself.  The candidate test
+// is decide()'s, as in P1Lane::step, but evaluated only behind a condition it
+// implies: kmer_regions needs best >= min_score; tr_lr needs pos(i) - pos(beg)
+// >= min_len in both of its clauses, and pos(i) - pos(beg) <= i - beg + 1, so
+// i - beg >= min_len - 1 (reach, clamped to int by the caller).  classify
+// (uniform over the block): the LUT holds a non-finite value, so every value is
+// classified; else special is known before the walk (see k_pass1c).
+//
+// The carried head is head_step as selects, with no branch (the caller has
+// tested i < n): act is hq < 0 carried from the index before.  T moves on after
+// the clamp, where nothing reads it (finish_exact takes T only from a head that
+// never clamped).  The head is walked at every index, also after every head of
+// the wave has clamped: skipping it then takes a second copy of the step per
+// wave state, which cost registers and with them resident waves, and pays only
+// where all 64 heads of a wave clamp early ("Kept-code
+// reader", has the measurement).
+template <bool kTrlr>
+__device__ __forceinline__ void code_index(P1Lane<false, kTrlr, true> &L, bool &pos, bool &act, double s, int i,
+                                           const EmitCfg &ec, int reach, const Cand &cand, bool classify) {
+  {
+    Head &h = L.hx;
+    const double t = h.T + s;
+    const bool tp = t > 0;
+    const double T = tp ? t : 0.0;
+    const bool hup = act & tp & (T > h.hmax);
+    h.hq = (act & !tp) ? i : h.hq;
+    h.hmax = hup ? T : h.hmax;
+    h.harg = hup ? i : h.harg;
+    h.T = T;
+    act = act & tp;
+  }
+  if (classify) L.special |= !isfinite(s);
+  const double tt = L.prev + s;
+  const bool pn = tt > 0;
+  const double S = pn ? tt : 0.0;
+  const bool open = !pos & pn;
+  const bool close = pos & !pn;
+  if (kTrlr ? (close & (i - L.beg >= reach)) : (close & (L.best >= ec.min_score))) {
+    const int f0 = L.f0, arg = L.arg, beg = L.beg;
+    const long long ml = kTrlr ? ec.min_len : 0;
+    const bool want =
+        kTrlr ? ((((long long)((arg != f0 ? arg - 1 : arg) - (beg != f0 ? beg - 1 : beg)) >= ml) |
+                  ((long long)((i != f0 ? i - 1 : i) - (arg != f0 ? arg - 1 : arg) - 1) >= (ml > 1 ? ml : 1LL))))
+              : ((uint64_t)(int64_t)(arg - beg) >= ec.mw);
+    if (want) cand_put(cand, L.start, beg, arg, i, L.best);
+  }
+  const bool up = open | (S > L.best);
+  L.best = up ? S : L.best;
+  L.arg = up ? i : L.arg;
+  L.beg = open ? i : L.beg;
+  L.prev = S;
+  pos = pn;
+}
+
+// A wave picks the form of its steps (the choices are uniform over the wave,
+// so no lane waits for another's branch):
+//  full -- all 64 lanes are live chunks of CH indices (one ballot): no i < n
+//    test, a step's J values are read from the LUT ahead of the step's walk
+//    (counted LDS waits), and the last step's live count is a constant.  One
+//    short chunk or a dead lane sends the wave, and only it, to the guarded
+//    form.  Both forms sit in the one chunk loop: every further copy of the loop
+//    (one per form, per phase of the head, per class flag) cost about ten
+//    VGPRs and with them waves per SIMD;
+//  classify, per block -- whether the LUT holds a non-finite value is found
+//    while it is staged; a non-finite first value (tr_lr) is noted once.
+#define KS_INLINE_LAMBDA __attribute__((always_inline))
 template <int J, bool kTrlr, bool kVisits>
-__global__ void __launch_bounds__(kCodeBlock) k_pass1c(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
+__global__ void __launch_bounds__(code_block(kVisits)) k_pass1c(Chunks g, int64_t total, int k, TableView tv, EmitCfg ec,
                                                        uint32_t *__restrict__ visits, P1 o, Cand cand,
                                                        const double *__restrict__ xh, Carry cr,
                                                        unsigned int *__restrict__ err,
                                                        const uint32_t *__restrict__ kc) {
   constexpr int NS = kc_steps(J), W = kc_words(J), D = kCodeDepth;
   constexpr int NG = (NS + D - 1) / D;
+  constexpr int kCodeBlock = code_block(kVisits);
+  constexpr int LAST = CH - (NS - 1) * J;  // indices of a full chunk's last step
+  static_assert((NG - 1) * D < NS && LAST >= 1 && LAST <= J, "only the last batch is short, only the last step partial");
   extern __shared__ double s_clut[];
-  for (int i = threadIdx.x; i < tv.nlut; i += kCodeBlock) s_clut[i] = tv.lut[i];
-  __syncthreads();
+  int bad = 0;
+  for (int i = threadIdx.x; i < tv.nlut; i += kCodeBlock) {
+    const double v = tv.lut[i];
+    s_clut[i] = v;
+    if (!kVisits) bad |= !isfinite(v);
+  }
+  // (kVisits classifies every value itself: P1Lane::step)
+  const bool lut_special = kVisits ? (__syncthreads(), false) : __syncthreads_or(bad) != 0;
   const int64_t c = g.c0 + (int64_t)blockIdx.x * kCodeBlock + threadIdx.x;
   if (c >= g.nch) return;
   const int64_t start = g.start[c];
   const int n = g.n[c];
   const bool first = c == 0 || g.run[c - 1] != g.run[c];
-  const uint32_t kmask = (1u << (2 * k)) - 1u;
   const uint32_t *__restrict__ rp = kc + kc_slot(c, 0, J);
   uint32_t cur[D][W] = {}, nxt[D][W] = {};
-  auto fetch = [&](int gi, uint32_t (&b)[D][W]) {
+  auto fetch = [&](int gi, uint32_t (&b)[D][W]) KS_INLINE_LAMBDA {
 #pragma unroll
     for (int d = 0; d < D; ++d)
       if (gi * D + d < NS) kc_load<W>(rp + (size_t)(gi * D + d) * 64 * W, b[d]);
@@ -2047,42 +2136,108 @@ __global__ void __launch_bounds__(kCodeBlock) k_pass1c(Chunks g, int64_t total, 
     if (kTrlr && first) first_val = ec.ks[km0];
     if ((c & 63) == 0 && (cur[0][0] & 0xffffu) != (uint32_t)tv.codes[km0]) atomicOr(err, 128u);
   }
-  LaneBases B;
-  uint64_t x = 0;
-  const uint64_t xmask = (1ull << (2 * (k + J - 1))) - 1ull;
-  if (kVisits) {
-    B.load(g.packed, total, start - k);
-    x = B.first_key(k + J - 1);
-  }
-  for (int gi = 0; gi < NG; ++gi) {
-    if (gi + 1 < NG) fetch(gi + 1, nxt);
-    if (gi * D * J < n) {  // (a short chunk's later batches: nothing to walk)
+  // (the one value that is not the LUT's: index 0 of a run's first chunk)
+  if (!kVisits && kTrlr && first && n > 0) L.special = !isfinite(first_val);
+  const long long rl = kTrlr ? (long long)ec.min_len - 1 : 0;
+  const int reach = (int)(rl < 0 ? 0 : (rl > CH ? CH + 1 : rl));
+  using std::integral_constant;
+  using std::true_type;
+  using std::false_type;
+  // step st (its record: r), LIVE indices of it
+  auto step = [&](auto full, auto live, int st, const uint32_t (&r)[W]) KS_INLINE_LAMBDA {
+    constexpr bool kFull = decltype(full)::value;
+    constexpr int LIVE = decltype(live)::value;
+    auto value = [&](int t) KS_INLINE_LAMBDA { return s_clut[(r[t >> 1] >> (16 * (t & 1))) & 0xffffu]; };
+    double v[LIVE];
+    if (kFull) {  // (guarded: a dead index's code is whatever the slot held, so it is read behind i < n)
 #pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const int st = gi * D + d;
-        if (st < NS) {
+      for (int t = 0; t < LIVE; ++t) v[t] = value(t);
+      if (kTrlr) v[0] = (first && st == 0) ? first_val : v[0];
+    }
+    bool pos = L.prev > 0, act = L.hx.hq < 0;
 #pragma unroll
-          for (int t = 0; t < J; ++t) {
-            const int i = st * J + t;
-            if (i < n) {
-              const uint32_t code = (cur[d][t >> 1] >> (16 * (t & 1))) & 0xffffu;
-              double sv = s_clut[code];
-              if (kTrlr && first && i == 0) sv = first_val;
-              if (kVisits) atomicAdd(&visits[(uint32_t)(x >> (2 * (J - 1 - t))) & kmask], 1u);
-              L.step(sv, i, ec, cand);
-            }
-          }
-          if (kVisits) x = B.next_key(x, J, xmask);
+    for (int t = 0; t < LIVE; ++t) {
+      const int i = st * J + t;
+      if (kFull || i < n) {
+        double sv;
+        if (kFull) {
+          sv = v[t];
+        } else {
+          sv = value(t);
+          if (kTrlr && first && i == 0) sv = first_val;
         }
+        code_index<kTrlr>(L, pos, act, sv, i, ec, reach, cand, lut_special);
       }
     }
+  };
+  auto walk = [&](bool full) KS_INLINE_LAMBDA {
+    auto either = [&](auto live, int st, const uint32_t (&r)[W]) KS_INLINE_LAMBDA {
+      if (full) step(true_type{}, live, st, r);
+      else step(false_type{}, live, st, r);
+    };
+    for (int gi = 0; gi < NG - 1; ++gi) {
+      fetch(gi + 1, nxt);
+      if (full || gi * D * J < n) {  // (a short chunk's later batches: nothing to walk)
 #pragma unroll
-    for (int d = 0; d < D; ++d)
+        for (int d = 0; d < D; ++d) either(integral_constant<int, J>{}, gi * D + d, cur[d]);
+      }
 #pragma unroll
-      for (int q = 0; q < W; ++q) cur[d][q] = nxt[d][q];
+      for (int d = 0; d < D; ++d)
+#pragma unroll
+        for (int q = 0; q < W; ++q) cur[d][q] = nxt[d][q];
+    }
+    if (full || (NG - 1) * D * J < n) {  // the last batch: steps (NG - 1) D .. NS - 1
+      auto rest = [&](auto self, auto dc) KS_INLINE_LAMBDA {
+        constexpr int d = decltype(dc)::value, st = (NG - 1) * D + d;
+        if constexpr (st < NS) {
+          either(integral_constant<int, (st == NS - 1 ? LAST : J)>{}, st, cur[d]);
+          self(self, integral_constant<int, d + 1>{});
+        }
+      };
+      rest(rest, integral_constant<int, 0>{});
+    }
+  };
+  if constexpr (kVisits) {
+    // One global atomic per index bounds this flavour, and the key walk's
+    // registers leave no room for the phases (they spilt): P1Lane's own step.
+    LaneBases B;
+    const uint32_t kmask = (1u << (2 * k)) - 1u;
+    const uint64_t xmask = (1ull << (2 * (k + J - 1))) - 1ull;
+    B.load(g.packed, total, start - k);
+    uint64_t x = B.first_key(k + J - 1);
+    for (int gi = 0; gi < NG; ++gi) {
+      if (gi + 1 < NG) fetch(gi + 1, nxt);
+      if (gi * D * J < n) {  // (a short chunk's later batches: nothing to walk)
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          const int st = gi * D + d;
+          if (st < NS) {
+#pragma unroll
+            for (int t = 0; t < J; ++t) {
+              const int i = st * J + t;
+              if (i < n) {
+                const uint32_t code = (cur[d][t >> 1] >> (16 * (t & 1))) & 0xffffu;
+                double sv = s_clut[code];
+                if (kTrlr && first && i == 0) sv = first_val;
+                atomicAdd(&visits[(uint32_t)(x >> (2 * (J - 1 - t))) & kmask], 1u);
+                L.step(sv, i, ec, cand);
+              }
+            }
+            x = B.next_key(x, J, xmask);
+          }
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < D; ++d)
+#pragma unroll
+        for (int q = 0; q < W; ++q) cur[d][q] = nxt[d][q];
+    }
+  } else {
+    walk(__ballot(n == CH) == ~0ull);
   }
   L.finish_exact(c, g, o, cr, xh, err);
 }
+#undef KS_INLINE_LAMBDA
 
 // KS_TEST_KEPT_CODES (tests): the kept codes of a call that reads them, spoilt
 // before its pass 1.  what 0 (sample): the first code of chunk 0, which the
@@ -4769,8 +4924,9 @@ ks_status pass1_half(const ScanCall &c, const ScanPlan &plan, const Work &w, con
         return pick_int<5, 7, 4>(plan.codes_J, [&](auto j) {
           return pick_bool(trlr, [&](auto t) {
             return pick_bool(c.visits != nullptr, [&](auto v) {
-              return launch(k_pass1c<decltype(j)::value, decltype(t)::value, decltype(v)::value>, blocks(kCodeBlock),
-                            dim3(kCodeBlock), (size_t)tv.nlut * 8, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand,
+              constexpr int kBlock = code_block(decltype(v)::value);
+              return launch(k_pass1c<decltype(j)::value, decltype(t)::value, decltype(v)::value>, blocks(kBlock),
+                            dim3(kBlock), (size_t)tv.nlut * 8, strm, gv, c.total, c.k, tv, ec, c.visits, p1, cand,
                             xh, cr, err, w.kc);
             });
           });
