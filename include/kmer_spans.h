@@ -702,9 +702,37 @@ int32_t ks_spectra_tile_bases(void);
  * All output offsets are 64-bit (the condensed form passes 2^31 entries at
  * m = 65,537).  The caller owns the output.  ctx == NULL is the default
  * context on device 0; the calls are never spread over a device list and are
- * not forwarded by the fork broker. */
+ * not forwarded by the fork broker.
+ *
+ * Metrics (R's dist(method=), and the Hellinger distance): bits 8 .. 11 of
+ * flags name the metric, KS_DIST_EUCLIDEAN (0, the text above) by default.
+ * The allowed bits are KS_DIST_SQUARED | KS_DIST_METRIC_MASK; a field value
+ * above KS_DIST_HELLINGER is "unknown distance metric N", and KS_DIST_SQUARED
+ * with manhattan, maximum or canberra is refused (the flag needs euclidean or
+ * hellinger).  p is the profile above; every operation below is a separate
+ * FP64 instruction, one accumulator per pair, k ascending:
+ *   manhattan: acc = 0; acc = acc + |p_i[k] - p_j[k]|.  The result is acc
+ *              (twice the total variation distance of the two profiles).
+ *   maximum:   acc = 0; t = |p_i[k] - p_j[k]|; acc = t > acc ? t : acc.  A NaN
+ *              t makes the result NaN.
+ *   canberra:  acc = 0, cnt = 0; s = p_i[k] + p_j[k]; a column with s == 0 is
+ *              omitted, otherwise acc = acc + |p_i[k] - p_j[k]| / s and
+ *              cnt = cnt + 1.  The result is acc if cnt == ncol, otherwise
+ *              acc / ((double)cnt / (double)ncol): R's rule (distance.c).
+ *   hellinger: q[k] = sqrt(p[k]), one correctly rounded root per profile
+ *              entry; acc is the Euclidean loop over q.  The result is
+ *              0.5 * acc with KS_DIST_SQUARED, otherwise sqrt(0.5 * acc): 0
+ *              between proportional rows, at most 1.
+ * In every metric d(i, j) has the bits of d(j, i), d(i, i) = 0, and a pair
+ * that involves a row with T = 0 is NaN. */
 #define KS_DIST_MAX_NCOL 4096
 #define KS_DIST_SQUARED 1
+#define KS_DIST_METRIC_MASK 0xf00
+#define KS_DIST_EUCLIDEAN 0x000
+#define KS_DIST_MANHATTAN 0x100
+#define KS_DIST_MAXIMUM 0x200
+#define KS_DIST_CANBERRA 0x300
+#define KS_DIST_HELLINGER 0x400
 typedef struct ks_dist_stats { /* hipEvent times on the ctx stream, ms */
   double ms_total, ms_normalise, ms_distance;
   int64_t n_pairs;       /* distances computed and written */
@@ -1421,7 +1449,17 @@ ks_status ks_spectra_kmeans_seed(ks_ctx *ctx, const uint32_t *spectra, int64_t n
  * Outputs, row-major, column 0 the nearest:
  *   index: int64 [na][k], 0-based positions into the candidate selection (not
  *          row indices);
- *   dist:  double [na][k], acc with KS_DIST_SQUARED, otherwise sqrt(acc). */
+ *   dist:  double [na][k], acc with KS_DIST_SQUARED, otherwise sqrt(acc).
+ *
+ * Metrics: flags takes the metric field of ks_spectra_dist (KS_DIST_METRIC_MASK),
+ * with the same checks, directly after the check of unknown flags.  The list
+ * is ordered by (value, position) as above.  The value is acc for euclidean
+ * and hellinger (the Euclidean loop over the rooted profiles; dist is then
+ * 0.5 * acc or sqrt(0.5 * acc)), and the returned distance for manhattan,
+ * maximum and canberra -- for canberra the result scaled by ncol / cnt.  Every
+ * value is non-negative and no NaN occurs (empty rows are refused).  Every
+ * returned distance carries the bits of ks_spectra_cross_dist with the same
+ * flags for that pair. */
 #define KS_KNN_MAX_K 64
 typedef struct ks_knn_stats { /* hipEvent times on the ctx stream, ms */
   double ms_total;

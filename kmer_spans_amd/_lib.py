@@ -162,6 +162,14 @@ KS_SPECTRA_MAX_Q = 6
 KS_SPECTRA_BOTH_STRANDS = 1
 KS_DIST_MAX_NCOL = 4096
 KS_DIST_SQUARED = 1
+KS_DIST_METRIC_MASK = 0xf00
+KS_DIST_EUCLIDEAN = 0x000
+KS_DIST_MANHATTAN = 0x100
+KS_DIST_MAXIMUM = 0x200
+KS_DIST_CANBERRA = 0x300
+KS_DIST_HELLINGER = 0x400
+DIST_METRICS = {"euclidean": KS_DIST_EUCLIDEAN, "manhattan": KS_DIST_MANHATTAN, "maximum": KS_DIST_MAXIMUM,
+                "canberra": KS_DIST_CANBERRA, "hellinger": KS_DIST_HELLINGER}
 HCLUST_METHODS = {"complete": 0, "single": 1, "average": 2}  # KS_HCLUST_*
 KS_HCLUST_KEEP_INPUT = 1
 KS_NJ_KEEP_INPUT = 1
@@ -483,6 +491,16 @@ def hclust_method(method) -> int:
     if method not in HCLUST_METHODS:
         raise KmerSpansError(f"method must be one of {sorted(HCLUST_METHODS)}, not {method!r}")
     return HCLUST_METHODS[method]
+
+
+def dist_flags(metric, squared) -> int:
+    """The flags of a distance or nearest-neighbour call: the metric's field
+    and KS_DIST_SQUARED, which only euclidean and hellinger have a form for."""
+    if metric not in DIST_METRICS:
+        raise KmerSpansError(f"metric must be one of {sorted(DIST_METRICS)}, not {metric!r}")
+    if squared and metric not in ("euclidean", "hellinger"):
+        raise KmerSpansError(f"squared=True has no meaning for metric={metric!r}: it needs 'euclidean' or 'hellinger'")
+    return DIST_METRICS[metric] | (KS_DIST_SQUARED if squared else 0)
 
 
 def hclust_outputs(n: int):

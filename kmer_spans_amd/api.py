@@ -233,15 +233,23 @@ def region_spectra(seq, pos, q: int = 4, both_strands: bool = True, seq_base: in
     return {"kmers": kmer_seq(q), "counts": counts, "freq": freq, "entropy": ent}
 
 
-def region_distances(counts, rows=None, rows_b=None, squared: bool = False, device: int = 0) -> np.ndarray:
-    """Euclidean distances between row-normalised spectra (R's dist() on
-    reg.kmer.sp, test.R:762-807) from the counts region_spectra returns.
+def region_distances(counts, rows=None, rows_b=None, squared: bool = False, device: int = 0,
+                     metric: str = "euclidean") -> np.ndarray:
+    """Distances between row-normalised spectra (R's dist() on reg.kmer.sp,
+    test.R:762-807) from the counts region_spectra returns; Euclidean unless
+    metric= says otherwise.
 
     counts: [n, ncol] non-negative integers (uint32 range), 1 <= ncol <= 4096.
     A row's profile is counts / row sum; the distance of two rows is the FP64
     sum over the columns, in order, of the squared profile differences --
     squared=True returns that sum, otherwise its square root.  An empty row
     is NaN against every row; rows with proportional counts are at exactly 0.
+    metric: "euclidean", or "manhattan", "maximum", "canberra" as in R's
+    dist(method=) (canberra omits the columns where both profiles are 0 and
+    scales the sum by ncol / columns kept), or "hellinger": sqrt(0.5 * the
+    squared Euclidean distance of the profiles' square roots), in [0, 1].
+    squared=True needs "euclidean" or "hellinger".  Every metric is a fixed
+    order of FP64 operations (include/kmer_spans.h).
     rows / rows_b: optional integer row indices (any order, repeats allowed).
     rows_b is None: the condensed form, float64[m(m-1)/2] over the pairs i < j
     of the selected rows (all rows when rows is None) in the order of R's dist
@@ -250,7 +258,7 @@ def region_distances(counts, rows=None, rows_b=None, squared: bool = False, devi
     c, n, ncol = _lib.counts_arg(counts)
     ra, na = _lib.rows_arg(rows, "rows", n)
     rb, nb = _lib.rows_arg(rows_b, "rows_b", 0)
-    flags = _lib.KS_DIST_SQUARED if squared else 0
+    flags = _lib.dist_flags(metric, squared)
     L = load()
     if rows_b is None:
         out = np.zeros(na * (na - 1) // 2 if na > 1 else 0, dtype=np.float64)
@@ -388,7 +396,8 @@ def region_kmeans_seed(counts, g, method: str = "maximin", rows=None, first=0, u
                 **_lib.seed_result(res))
 
 
-def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device: int = 0):
+def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device: int = 0,
+               metric: str = "euclidean"):
     """The k nearest regions of every region by spectrum, computed on the
     device without the distance matrix: memory is the profile panel plus
     O(na k), and nothing of size na x nb is written or sorted.
@@ -402,19 +411,23 @@ def region_knn(counts, k, rows=None, rows_b=None, squared: bool = False, device:
     exceed the number of candidates (na - 1 in the self form).  A selected row
     without counts is an error naming its position.  The distance is
     region_distances': squared=True returns the FP64 sum of squared profile
-    differences, otherwise its square root.  Returns (index, dist): int64
+    differences, otherwise its square root; metric= names another metric as in
+    region_distances, and every returned distance has the bits region_distances
+    gives for that pair.  Returns (index, dist): int64
     [na, k] positions into the candidate selection (not row indices) and
     float64 [na, k], column 0 the nearest; the k candidates with the smallest
     (squared distance, position), ascending, so ties go to the lowest position
-    and the same input gives the same bits on every run."""
+    and the same input gives the same bits on every run ("manhattan",
+    "maximum" and "canberra" rank by the distance itself)."""
     c, n, ncol = _lib.counts_arg(counts)
     ra, na = _lib.rows_arg(rows, "rows", n)
     rb, nb = _lib.rows_arg(rows_b, "rows_b", 0)
     k, kb = _lib.knn_k(k)
+    flags = _lib.dist_flags(metric, squared)
     index = np.zeros((max(na, 0), kb), dtype=np.int64)
     dist = np.zeros((max(na, 0), kb), dtype=np.float64)
     check(load().ks_spectra_knn(_ctx(device), c.ctypes.data, n, ncol, host_ptr(ra), na, host_ptr(rb), nb, k,
-                                _lib.KS_DIST_SQUARED if squared else 0, index.ctypes.data, dist.ctypes.data))
+                                flags, index.ctypes.data, dist.ctypes.data))
     return index, dist
 
 

@@ -398,7 +398,8 @@ ks_status km_normalise(ks_ctx *ctx, const KmWork &w, const uint32_t *sp, int64_t
                        int64_t m, const double *init, const int64_t *init_rows, int g) {
   hipStream_t st = ctx->stream;
   KS_HIP(hipMemsetAsync(w.state, 0, sizeof(KmState), st));
-  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, w.panel, w.iota, &w.state->bad[0], &w.state->bad[1]));
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, PanelRoot::kNone, w.panel, w.iota, &w.state->bad[0],
+                         &w.state->bad[1]));
   if (init) {
     const int64_t total = (int64_t)g * ncol;
     const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)ctx->num_cus * 8);

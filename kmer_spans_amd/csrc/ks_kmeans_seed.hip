@@ -318,7 +318,7 @@ ks_status seed_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   w.lay(static_cast<char *>(mem.p), m, ncol, g, nch);
   KS_HIP(hipEventRecord(ctx->ev[0], st));
   KS_HIP(hipMemsetAsync(w.bad, 0, 16, st));
-  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, w.panel, nullptr, &w.bad[0], &w.bad[1]));
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, PanelRoot::kNone, w.panel, nullptr, &w.bad[0], &w.bad[1]));
   if (dsq) KS_HIP(hipMemcpyAsync(w.ud, u, (size_t)g * 8, hipMemcpyHostToDevice, st));
   unsigned long long hbad[2] = {0, 0};
   KS_HIP(hipMemcpyAsync(hbad, w.bad, sizeof(hbad), hipMemcpyDeviceToHost, st));

@@ -39,6 +39,14 @@
 //            first entry that does not beat the k-th.  It takes the root if
 //            asked and writes index and dist.  With one split k_knn_select
 //            writes them itself.
+// Metrics:   the kernels are templates on the metric field of flags
+//            (ks_dist_metric.h).  The lists hold the value a
+//            pair is ranked by: acc for euclidean and hellinger (the panel
+//            holds the roots then), the distance itself for manhattan, maximum
+//            and canberra (canberra's acc is scaled by its count after a
+//            tile's last chunk).  All values are >= +0 and never NaN, so the
+//            insertion and the merge are the same code for every metric; only
+//            the last step (root, 0.5 *) differs.
 // No kernel waits on another workgroup; stream order is the only
 // synchronisation between them.
 #include <algorithm>
@@ -47,6 +55,8 @@
 #include <limits>
 
 #include "ks_panel.h"
+// after hip_runtime.h (ks_internal.h)
+#include "ks_dist_metric.h"
 
 namespace ks {
 namespace {
@@ -85,6 +95,8 @@ __device__ __forceinline__ int knn_insert(double &lv, int &lp, double v, int j, 
 // Block (x, y): query rows [64 x, 64 x + 64) against the candidate tiles [y tps, (y + 1) tps).
 // direct: index / dist [na][k] are written; otherwise pval / ppos [y][na][k], the split's sorted list,
 // unused entries (+inf, kNoPos).  self: candidate position == query position is left out.
+// M: the metric (ks_dist_metric.h); the lists hold metric_value, the value the pairs are ranked by.
+template <int M>
 __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ pa, int64_t na,
                                                     const double *__restrict__ pb, int64_t nb, int ncol, int k,
                                                     int self, int tps, int direct, int take_root,
@@ -110,10 +122,11 @@ __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ p
   for (int t = t0; t < t1; ++t) {
     const int64_t j0 = (int64_t)t * kNT;
     double acc[4][4];
+    int cnt[4][4];  // canberra's columns kept; no register in the other metrics
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[r][e] = 0.0;
+      for (int e = 0; e < 4; ++e) acc[r][e] = 0.0, cnt[r][e] = 0;
     for (int k0 = 0; k0 < ncol; k0 += kNK) {
 #pragma unroll
       for (int e = 0; e < kNK * kNT / 256; ++e) {
@@ -124,7 +137,8 @@ __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ p
         Bs[ka][ra] = (in_k && j0 + ra < nb) ? pb[(size_t)(j0 + ra) * ncol + k0 + ka] : 0.0;
       }
       __syncthreads();
-      // columns past ncol are staged as zeros on both sides: acc + 0 * 0 leaves acc's bits
+      // columns past ncol are staged as zeros on both sides: they leave acc's bits in every metric, and
+      // canberra omits them without counting them (metric_step)
 #pragma unroll
       for (int kk = 0; kk < kNK; ++kk) {
         double a[4], b[4];
@@ -135,12 +149,15 @@ __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ p
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const double d = a[r] - b[e];
-            acc[r][e] = acc[r][e] + d * d;
-          }
+          for (int e = 0; e < 4; ++e) metric_step<M>(acc[r][e], cnt[r][e], a[r], b[e]);
       }
       __syncthreads();
+    }
+    if constexpr (M == KS_DIST_CANBERRA) {  // ranked by the scaled result (a pair past the edges: 0 / 0, masked below)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[r][e] = metric_value<M>(acc[r][e], cnt[r][e], ncol);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -191,7 +208,7 @@ __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ p
     const int p = lpos[(wrow + q) * k + lane];
     if (direct) {
       index[(size_t)i * k + lane] = p;
-      dist[(size_t)i * k + lane] = take_root ? sqrt(v) : v;
+      dist[(size_t)i * k + lane] = metric_result<M>(v, !take_root);
     } else {
       const size_t o = ((size_t)blockIdx.y * na + i) * k + lane;
       pval[o] = v, ppos[o] = p;
@@ -200,6 +217,7 @@ __global__ void __launch_bounds__(256) k_knn_select(const double *__restrict__ p
 }
 
 // A wave per query row: the nsplit sorted lists pval / ppos [y][na][k] into index / dist [na][k].
+template <int M>
 __global__ void __launch_bounds__(256) k_knn_merge(const double *__restrict__ pval, const int *__restrict__ ppos,
                                                    int64_t na, int k, int nsplit, int take_root,
                                                    int64_t *__restrict__ index, double *__restrict__ dist) {
@@ -224,7 +242,7 @@ __global__ void __launch_bounds__(256) k_knn_merge(const double *__restrict__ pv
   }
   if (lane >= k) return;
   index[(size_t)i * k + lane] = lp;
-  dist[(size_t)i * k + lane] = take_root ? sqrt(lv) : lv;
+  dist[(size_t)i * k + lane] = metric_result<M>(lv, !take_root);
 }
 
 // The work memory of a call, one allocation: the panel, then the rest.
@@ -260,8 +278,9 @@ ks_status check_knn_args(const void *spectra, int64_t n, int32_t ncol, const voi
   KS_TRY(panel_check_ncol(ncol, KS_DIST_MAX_NCOL));
   if (k < 1 || k > KS_KNN_MAX_K)
     return fail(KS_ERR_ARG, "k must be between 1 and %d (k = %d)", KS_KNN_MAX_K, (int)k);
-  if (flags & ~KS_DIST_SQUARED)
+  if (flags & ~(KS_DIST_SQUARED | KS_DIST_METRIC_MASK))
     return fail(KS_ERR_ARG, "unknown flags 0x%x for a nearest-neighbour call", (unsigned)flags);
+  KS_TRY(dist_check_metric(flags));
   KS_TRY(panel_check_n(n));
   KS_TRY(panel_check_null_rows(rows, na, n, "rows", "na"));
   if (!spectra) return fail(KS_ERR_ARG, "null spectra");
@@ -302,7 +321,8 @@ void split_plan(int64_t na, int64_t ncand, int ncol, int k, int64_t slots, int *
 }
 
 // Everything but the device-side checks validated; all pointers are device pointers.
-ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const int64_t *rows, int64_t na,
+template <int M>
+ks_status knn_metric(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const int64_t *rows, int64_t na,
                    const int64_t *rows_b, int64_t nb, int k, int flags, int64_t *index, double *dist,
                    ks_knn_stats *stats) {
   hipStream_t st = ctx->stream;
@@ -311,9 +331,9 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   KnnWork w;
   DevFree mem;
   const size_t lds = (size_t)kNT * k * 12;
-  KS_HIP(hipFuncSetAttribute((const void *)k_knn_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KS_HIP(hipFuncSetAttribute((const void *)k_knn_select<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 1;  // workgroups of k_knn_select a CU holds at this k (registers, and the lists' LDS)
-  KS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_knn_select, 256, lds));
+  KS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_knn_select<M>, 256, lds));
   split_plan(na, ncand, ncol, k, (int64_t)ctx->num_cus * std::max(per_cu, 1), &w.tps, &w.nsplit);
   w.lay(nullptr, na, self ? 0 : nb, ncol, k);
   KS_TRY(dev_alloc(&mem, w.bytes, "the profile panel"));
@@ -321,8 +341,10 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
 
   KS_HIP(hipEventRecord(ctx->ev[0], st));
   KS_HIP(hipMemsetAsync(w.state, 0, sizeof(KnnState), st));
-  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, na, w.pa, nullptr, &w.state->bad[0], &w.state->bad[2]));
-  if (!self) KS_TRY(panel_normalise(ctx, sp, n, ncol, rows_b, nb, w.pb, nullptr, &w.state->bad[1], &w.state->bad[3]));
+  const PanelRoot root = M == KS_DIST_HELLINGER ? PanelRoot::kSqrt : PanelRoot::kNone;
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, na, root, w.pa, nullptr, &w.state->bad[0], &w.state->bad[2]));
+  if (!self)
+    KS_TRY(panel_normalise(ctx, sp, n, ncol, rows_b, nb, root, w.pb, nullptr, &w.state->bad[1], &w.state->bad[3]));
   unsigned long long hbad[4] = {0, 0, 0, 0};
   KS_HIP(hipMemcpyAsync(hbad, w.state->bad, sizeof(hbad), hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));
@@ -331,13 +353,13 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   // from here on the outputs are written
   KS_HIP(hipEventRecord(ctx->ev[1], st));
   const int take_root = (flags & KS_DIST_SQUARED) ? 0 : 1;
-  hipLaunchKernelGGL(k_knn_select, dim3((unsigned)((na + kNT - 1) / kNT), (unsigned)w.nsplit), dim3(256), lds, st,
+  hipLaunchKernelGGL(k_knn_select<M>, dim3((unsigned)((na + kNT - 1) / kNT), (unsigned)w.nsplit), dim3(256), lds, st,
                      w.pa, na, w.pb, ncand, ncol, k, self ? 1 : 0, w.tps, w.nsplit == 1 ? 1 : 0, take_root, w.pval,
                      w.ppos, index, dist);
   KS_HIP(hipGetLastError());
   KS_HIP(hipEventRecord(ctx->ev[2], st));
   if (w.nsplit > 1) {
-    hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, st, w.pval, w.ppos, na, k, w.nsplit,
+    hipLaunchKernelGGL(k_knn_merge<M>, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, st, w.pval, w.ppos, na, k, w.nsplit,
                        take_root, index, dist);
     KS_HIP(hipGetLastError());
   }
@@ -355,6 +377,14 @@ ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
     stats->work_bytes = (int64_t)(w.bytes - w.panel_bytes);
   }
   return KS_OK;
+}
+
+ks_status knn_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const int64_t *rows, int64_t na,
+                   const int64_t *rows_b, int64_t nb, int k, int flags, int64_t *index, double *dist,
+                   ks_knn_stats *stats) {
+  return metric_dispatch(flags, [&](auto metric) {
+    return knn_metric<decltype(metric)::value>(ctx, sp, n, ncol, rows, na, rows_b, nb, k, flags, index, dist, stats);
+  });
 }
 
 }  // namespace

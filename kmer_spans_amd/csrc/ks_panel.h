@@ -21,13 +21,23 @@ ks_status panel_check_null_rows(const void *rows, int64_t cnt, int64_t n, const 
 // The checks k-means, group means and seeding share: m >= 1, ncol <= KS_DIST_MAX_NCOL, no flags.
 ks_status panel_check_common(int64_t n, int32_t ncol, const void *rows, int64_t m, int32_t flags, const char *what);
 
+// The metric field of distance flags whose other bits the caller has checked:
+// "unknown distance metric N" above KS_DIST_HELLINGER, and KS_DIST_SQUARED is
+// refused with a metric that has no squared form.
+ks_status dist_check_metric(int32_t flags);
+
+// What a panel entry is: the profile p, or its root (the Hellinger panel).
+enum class PanelRoot { kNone, kSqrt };
+
 // Queues k_panel_normalise on ctx->stream for one selection (rows null: rows
-// 0 .. cnt - 1): panel[s][c] = count / row sum, row-major [cnt][ncol]; iota
+// 0 .. cnt - 1): panel[s][c] = count / row sum, row-major [cnt][ncol]; with
+// PanelRoot::kSqrt the correctly rounded root of that.  iota
 // (may be null): iota[s] = s.  bad_index / bad_empty (device words the caller
 // zeroed): cnt - s of the first bad row index / of the first row without
 // counts, by atomicMax.  No synchronisation: the caller reads the words back.
 ks_status panel_normalise(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const int64_t *rows, int64_t cnt,
-                          double *panel, int *iota, unsigned long long *bad_index, unsigned long long *bad_empty);
+                          PanelRoot root, double *panel, int *iota, unsigned long long *bad_index,
+                          unsigned long long *bad_empty);
 // The words read back, for one or two selections (sides): bad[0 .. sides) are
 // the bad_index words, bad[sides .. 2 sides) the bad_empty words.  The first
 // selection's index comes first, then the second's, then the empty rows.

@@ -12,6 +12,8 @@
 
 namespace ks {
 
+// kRoot: the entry is sqrt(p) (PanelRoot::kSqrt); the instantiation without it is the kernel of every other caller.
+template <bool kRoot>
 __global__ void __launch_bounds__(256) k_panel_normalise(const uint32_t *__restrict__ sp, int64_t n, int ncol,
                                                          const int64_t *__restrict__ rows, int64_t cnt,
                                                          double *__restrict__ panel, int *__restrict__ iota,
@@ -38,7 +40,10 @@ __global__ void __launch_bounds__(256) k_panel_normalise(const uint32_t *__restr
   }
   const double tot = (double)t;  // below 2^44: exact
   double *dst = panel + (size_t)s * ncol;
-  for (int c = lane; c < ncol; c += 64) dst[c] = (double)row[c] / tot;
+  for (int c = lane; c < ncol; c += 64) {
+    const double p = (double)row[c] / tot;
+    dst[c] = kRoot ? sqrt(p) : p;
+  }
 }
 
 namespace {
@@ -86,10 +91,26 @@ ks_status panel_check_common(int64_t n, int32_t ncol, const void *rows, int64_t 
   return panel_check_null_rows(rows, m, n, "rows", "m");
 }
 
+ks_status dist_check_metric(int32_t flags) {
+  static const char *const kName[] = {"euclidean", "manhattan", "maximum", "canberra", "hellinger"};
+  const int metric = flags & KS_DIST_METRIC_MASK;
+  if (metric > KS_DIST_HELLINGER) return fail(KS_ERR_ARG, "unknown distance metric %d", metric >> 8);
+  if ((flags & KS_DIST_SQUARED) && metric != KS_DIST_EUCLIDEAN && metric != KS_DIST_HELLINGER)
+    return fail(KS_ERR_ARG, "KS_DIST_SQUARED has no meaning for the %s metric: the flag needs euclidean or hellinger",
+                kName[metric >> 8]);
+  return KS_OK;
+}
+
 ks_status panel_normalise(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const int64_t *rows, int64_t cnt,
-                          double *panel, int *iota, unsigned long long *bad_index, unsigned long long *bad_empty) {
-  hipLaunchKernelGGL(k_panel_normalise, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, ctx->stream, sp, n, ncol, rows,
-                     cnt, panel, iota, bad_index, bad_empty);
+                          PanelRoot root, double *panel, int *iota, unsigned long long *bad_index,
+                          unsigned long long *bad_empty) {
+  const dim3 grid((unsigned)((cnt + 3) / 4));
+  if (root == PanelRoot::kSqrt)
+    hipLaunchKernelGGL(k_panel_normalise<true>, grid, dim3(256), 0, ctx->stream, sp, n, ncol, rows, cnt, panel, iota,
+                       bad_index, bad_empty);
+  else
+    hipLaunchKernelGGL(k_panel_normalise<false>, grid, dim3(256), 0, ctx->stream, sp, n, ncol, rows, cnt, panel, iota,
+                       bad_index, bad_empty);
   KS_HIP(hipGetLastError());
   return KS_OK;
 }

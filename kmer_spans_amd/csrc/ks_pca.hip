@@ -395,7 +395,7 @@ ks_status pca_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const i
   // profiles; every index and every row sum is checked before any output is written
   KS_HIP(hipEventRecord(ctx->ev[0], st));
   KS_HIP(hipMemsetAsync(state, 0, sizeof(PcaState), st));
-  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, panel, nullptr, &state->bad[0], &state->bad[1]));
+  KS_TRY(panel_normalise(ctx, sp, n, ncol, rows, m, PanelRoot::kNone, panel, nullptr, &state->bad[0], &state->bad[1]));
   unsigned long long hbad[2] = {0, 0};
   KS_HIP(hipMemcpyAsync(hbad, state->bad, 16, hipMemcpyDeviceToHost, st));
   KS_HIP(hipStreamSynchronize(st));

@@ -34,12 +34,21 @@
 //            The condensed form launches the T(T + 1)/2 tiles on or above the
 //            diagonal as a linear grid (ks_dist_index.h); diagonal tiles mask
 //            i >= j; ragged edges are masked, no load leaves the panel.
+// Metrics:   bits 8 .. 11 of flags (KS_DIST_METRIC_MASK).  The
+//            distance kernel is a template on the metric and takes its
+//            per-column step and its last step from ks_dist_metric.h; the
+//            Euclidean instantiation is the kernel described above.  Hellinger
+//            is that loop over a panel of roots (k_dist_normalise<true>) and a
+//            final 0.5 *; canberra keeps a count per pair next to acc; the
+//            maximum reads both rows' first panel entry in its last step,
+//            because the hardware maximum drops the NaN of an empty row.
 #include <cmath>
 #include <cstring>
 
 #include "ks_panel.h"
 // after hip_runtime.h (ks_internal.h): the header's functions are __host__ __device__ here
 #include "ks_dist_index.h"
+#include "ks_dist_metric.h"
 
 namespace ks {
 namespace {
@@ -63,7 +72,8 @@ __global__ void __launch_bounds__(256) k_dist_check(const int64_t *__restrict__ 
 }
 
 // Rows [s0, s0 + 64) of a selection (rows == nullptr: the rows themselves) ->
-// panel[k * ld + poff + s], k-major.
+// panel[k * ld + poff + s], k-major.  kRoot: the entry is sqrt(p), the Hellinger panel.
+template <bool kRoot>
 __global__ void __launch_bounds__(256) k_dist_normalise(const uint32_t *__restrict__ sp, int ncol,
                                                         const int64_t *__restrict__ rows, int64_t cnt,
                                                         double *__restrict__ panel, int64_t ld, int64_t poff) {
@@ -94,8 +104,10 @@ __global__ void __launch_bounds__(256) k_dist_normalise(const uint32_t *__restri
     __syncthreads();
     for (int kk = wv; kk < kDT; kk += 4) {
       const int k = c0 + kk;
-      if (k < ncol && s0 + lane < cnt)
-        panel[(size_t)k * ld + poff + s0 + lane] = (double)tile[lane][kk] / tot[lane];  // 0 / 0 = NaN: an empty row
+      if (k < ncol && s0 + lane < cnt) {
+        const double p = (double)tile[lane][kk] / tot[lane];  // 0 / 0 = NaN: an empty row
+        panel[(size_t)k * ld + poff + s0 + lane] = kRoot ? sqrt(p) : p;
+      }
     }
     __syncthreads();
   }
@@ -105,8 +117,9 @@ __global__ void __launch_bounds__(256) k_dist_normalise(const uint32_t *__restri
 // j < mb.  kCondensed: a0 = b0 = 0, ma = mb = m, blockIdx.x is a linear id over
 // the tiles on or above the diagonal, only i < j is stored, at
 // dist_pair_offset.  Otherwise blockIdx.x = tile row * tiles_b + tile column
-// and the output is the dense ma x mb block.
-template <bool kCondensed>
+// and the output is the dense ma x mb block.  M: the metric (ks_dist_metric.h); the
+// panel holds the roots for hellinger.
+template <int M, bool kCondensed>
 __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restrict__ panel, int64_t ld, int ncol,
                                                          int64_t a0, int64_t ma, int64_t b0, int64_t mb, int64_t tiles_b,
                                                          int squared, double *__restrict__ out) {
@@ -122,10 +135,11 @@ __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restric
   const int64_t i0 = tr * kDT, j0 = tc * kDT;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   double acc[4][4];
+  int cnt[4][4];  // canberra's columns kept; no register in the other metrics
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[r][e] = 0.0;
+    for (int e = 0; e < 4; ++e) acc[r][e] = 0.0, cnt[r][e] = 0;
 
   for (int k0 = 0; k0 < ncol; k0 += kDK) {
     const int kc = min(kDK, ncol - k0);
@@ -150,10 +164,7 @@ __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restric
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const double d = a[r] - b[e];
-            acc[r][e] = acc[r][e] + d * d;
-          }
+          for (int e = 0; e < 4; ++e) metric_step<M>(acc[r][e], cnt[r][e], a[r], b[e]);
       }
     } else {
       for (int kk = 0; kk < kc; ++kk) {
@@ -165,10 +176,7 @@ __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restric
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const double d = a[r] - b[e];
-            acc[r][e] = acc[r][e] + d * d;
-          }
+          for (int e = 0; e < 4; ++e) metric_step<M>(acc[r][e], cnt[r][e], a[r], b[e]);
       }
     }
     __syncthreads();
@@ -179,13 +187,21 @@ __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restric
   for (int r = 0; r < 4; ++r) {
     const int64_t i = i0 + ty * 4 + r;
     if (i >= ma) continue;
+    // maximum: a row without counts is NaN in every column, so its first entry tells
+    double nan_i = 0.0;
+    if constexpr (M == KS_DIST_MAXIMUM) nan_i = panel[a0 + i];
     // condensed: row i's entries start at pair (i, i + 1); its j-th sits j - i - 1 further
     const int64_t row0 = kCondensed ? dist_pair_offset(i, i + 1, ma) - (i + 1) : i * mb;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int64_t j = j0 + tx + 16 * e;
       if (j >= mb || (kCondensed && i >= j)) continue;
-      out[row0 + j] = squared ? acc[r][e] : sqrt(acc[r][e]);
+      double v = metric_value<M>(acc[r][e], cnt[r][e], ncol);
+      if constexpr (M == KS_DIST_MAXIMUM) {
+        const double mark = nan_i + panel[b0 + j];  // NaN where either row is
+        v = mark != mark ? mark : v;
+      }
+      out[row0 + j] = metric_result<M>(v, squared);
     }
   }
 }
@@ -194,7 +210,7 @@ __global__ void __launch_bounds__(kDThreads) k_dist_tile(const double *__restric
 // Comparison build (tools/spectra_dist_bench.py): one thread per
 // pair, both rows read from the panel in global memory for every pair.  The
 // same operation order, so the same bits.
-template <bool kCondensed>
+template <int M, bool kCondensed>
 __global__ void __launch_bounds__(kNaive *kNaive) k_dist_naive(const double *__restrict__ panel, int64_t ld, int ncol,
                                                                int64_t a0, int64_t ma, int64_t b0, int64_t mb,
                                                                int64_t tiles_b, int squared, double *__restrict__ out) {
@@ -209,11 +225,14 @@ __global__ void __launch_bounds__(kNaive *kNaive) k_dist_naive(const double *__r
   if (i >= ma || j >= mb || (kCondensed && i >= j)) return;
   const double *pa = panel + a0 + i, *pb = panel + b0 + j;
   double acc = 0.0;
-  for (int k = 0; k < ncol; ++k) {
-    const double d = pa[(size_t)k * ld] - pb[(size_t)k * ld];
-    acc = acc + d * d;
+  int cnt = 0;
+  for (int k = 0; k < ncol; ++k) metric_step<M>(acc, cnt, pa[(size_t)k * ld], pb[(size_t)k * ld]);
+  double v = metric_value<M>(acc, cnt, ncol);
+  if constexpr (M == KS_DIST_MAXIMUM) {
+    const double mark = pa[0] + pb[0];  // NaN where either row is
+    v = mark != mark ? mark : v;
   }
-  out[kCondensed ? dist_pair_offset(i, j, ma) : i * mb + j] = squared ? acc : sqrt(acc);
+  out[kCondensed ? dist_pair_offset(i, j, ma) : i * mb + j] = metric_result<M>(v, squared);
 }
 #endif
 
@@ -228,7 +247,9 @@ int64_t dist_grid(bool cross, int64_t ma, int64_t mb, int64_t *tiles_b) {
 
 ks_status check_dist_args(bool cross, int64_t n, int32_t ncol, int64_t ma, int64_t mb, int32_t flags) {
   KS_TRY(panel_check_ncol(ncol, KS_DIST_MAX_NCOL));
-  if (flags & ~KS_DIST_SQUARED) return fail(KS_ERR_ARG, "unknown distance flags 0x%x", (unsigned)flags);
+  if (flags & ~(KS_DIST_SQUARED | KS_DIST_METRIC_MASK))
+    return fail(KS_ERR_ARG, "unknown distance flags 0x%x", (unsigned)flags);
+  KS_TRY(dist_check_metric(flags));
   KS_TRY(panel_check_n(n));
   if (ma < 0 || mb < 0) return fail(KS_ERR_ARG, "the number of selected rows must not be negative");
   int64_t tb;
@@ -271,33 +292,34 @@ ks_status dist_impl(ks_ctx *ctx, const uint32_t *sp, int64_t n, int ncol, const 
   double *panel = static_cast<double *>(panel_mem.p);
 
   KS_HIP(hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(k_dist_normalise, dim3((unsigned)((ma + kDT - 1) / kDT)), dim3(256), 0, st, sp, ncol, rows_a, ma,
-                     panel, ld, (int64_t)0);
+  const bool root = (flags & KS_DIST_METRIC_MASK) == KS_DIST_HELLINGER;
+  const auto normalise = root ? k_dist_normalise<true> : k_dist_normalise<false>;
+  hipLaunchKernelGGL(normalise, dim3((unsigned)((ma + kDT - 1) / kDT)), dim3(256), 0, st, sp, ncol, rows_a, ma, panel,
+                     ld, (int64_t)0);
   KS_HIP(hipGetLastError());
   if (cross) {
-    hipLaunchKernelGGL(k_dist_normalise, dim3((unsigned)((mb + kDT - 1) / kDT)), dim3(256), 0, st, sp, ncol, rows_b, mb,
-                       panel, ld, ma);
+    hipLaunchKernelGGL(normalise, dim3((unsigned)((mb + kDT - 1) / kDT)), dim3(256), 0, st, sp, ncol, rows_b, mb, panel,
+                       ld, ma);
     KS_HIP(hipGetLastError());
   }
   KS_HIP(hipEventRecord(ctx->ev[1], st));
   const int sq = (flags & KS_DIST_SQUARED) ? 1 : 0;
   int64_t tb = 0;
   const int64_t grid = dist_grid(cross, ma, mb, &tb);  // (check_dist_args: it fits)
+  metric_dispatch(flags, [&](auto metric) {
+    constexpr int M = decltype(metric)::value;
 #ifdef KS_DIST_NAIVE
-  if (cross)
-    hipLaunchKernelGGL(k_dist_naive<false>, dim3((unsigned)grid), dim3(kNaive * kNaive), 0, st, panel, ld, ncol,
-                       (int64_t)0, ma, ma, mb, tb, sq, out);
-  else
-    hipLaunchKernelGGL(k_dist_naive<true>, dim3((unsigned)grid), dim3(kNaive * kNaive), 0, st, panel, ld, ncol,
-                       (int64_t)0, ma, (int64_t)0, ma, tb, sq, out);
+    const auto kernel = cross ? k_dist_naive<M, false> : k_dist_naive<M, true>;
+    const dim3 block(kNaive * kNaive);
 #else
-  if (cross)
-    hipLaunchKernelGGL(k_dist_tile<false>, dim3((unsigned)grid), dim3(kDThreads), 0, st, panel, ld, ncol, (int64_t)0,
-                       ma, ma, mb, tb, sq, out);
-  else
-    hipLaunchKernelGGL(k_dist_tile<true>, dim3((unsigned)grid), dim3(kDThreads), 0, st, panel, ld, ncol, (int64_t)0,
-                       ma, (int64_t)0, ma, tb, sq, out);
+    const auto kernel = cross ? k_dist_tile<M, false> : k_dist_tile<M, true>;
+    const dim3 block(kDThreads);
 #endif
+    // the cross form's B rows sit behind the A rows in the panel; the condensed form has one set
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), block, 0, st, panel, ld, ncol, (int64_t)0, ma,
+                       cross ? ma : (int64_t)0, cross ? mb : ma, tb, sq, out);
+    return KS_OK;
+  });
   KS_HIP(hipGetLastError());
   KS_HIP(hipEventRecord(ctx->ev[2], st));
   KS_HIP(hipStreamSynchronize(st));  // the panel is freed on return

@@ -561,9 +561,11 @@ def _dist_dev(dist, least):
 
 
 def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=None, squared: bool = False,
-                     out: torch.Tensor | None = None):
-    """ks_spectra_dist_dev / ks_spectra_cross_dist_dev: Euclidean distances
-    between the row-normalised spectra of region_spectra, on the device.
+                     out: torch.Tensor | None = None, metric: str = "euclidean"):
+    """ks_spectra_dist_dev / ks_spectra_cross_dist_dev: distances between the
+    row-normalised spectra of region_spectra, on the device; Euclidean unless
+    metric= names "manhattan", "maximum", "canberra" or "hellinger" (as in
+    api.region_distances; squared=True needs "euclidean" or "hellinger").
 
     counts: the int32 CUDA tensor [n, ncol] region_spectra returns (uint32
     bits), used in place.  rows / rows_b: optional selections of row indices,
@@ -591,7 +593,7 @@ def region_distances(ctx: _lib.Context, counts: torch.Tensor, rows=None, rows_b=
     else:
         res = torch.empty(shape, dtype=torch.float64, device=dev)
     st = _lib.DistStats()
-    flags = _lib.KS_DIST_SQUARED if squared else 0
+    flags = _lib.dist_flags(metric, squared)
     _order(ctx)
     if rb is None:
         check(load().ks_spectra_dist_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(ra), na, flags,
@@ -824,7 +826,8 @@ def region_kmeans_seed(ctx: _lib.Context, counts: torch.Tensor, g, method: str =
     return res, st.as_dict()
 
 
-def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=None, squared: bool = False):
+def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=None, squared: bool = False,
+               metric: str = "euclidean"):
     """ks_spectra_knn_dev: the k nearest rows of a candidate selection for
     every selected row of the spectra of region_spectra, on the device and
     without any distance matrix (memory: the profile panel plus O(na k)).
@@ -841,18 +844,22 @@ def region_knn(ctx: _lib.Context, counts: torch.Tensor, k, rows=None, rows_b=Non
     of positions into the candidate selection, a float64 CUDA tensor [na, k]
     (the squared sum with squared=True, otherwise its root), column 0 the
     nearest, ordered by (squared distance, position); stats the dict of
-    ks_knn_stats."""
+    ks_knn_stats.  metric= as in region_distances: "manhattan", "maximum" and
+    "canberra" rank by the distance itself, "hellinger" by the squared
+    Euclidean distance of the rooted profiles; every returned distance has the
+    bits region_distances gives for that pair."""
     dev, n, ncol = _counts_dev(counts)
     ra, na = _rows_dev(rows, "rows", dev, n)
     rb, nb = _rows_dev(rows_b, "rows_b", dev, 0)
     if rb is not None and not nb:
         raise _lib.KmerSpansError("rows_b names no row")
     k, kb = _lib.knn_k(k)
+    flags = _lib.dist_flags(metric, squared)
     index = torch.empty((na, kb), dtype=torch.int64, device=dev)
     dist = torch.empty((na, kb), dtype=torch.float64, device=dev)
     st = _lib.KnnStats()
     _order(ctx)
     check(load().ks_spectra_knn_dev(_handle(ctx), C.c_void_p(counts.data_ptr()), n, ncol, _ptr(ra), na, _ptr(rb), nb,
-                                    k, _lib.KS_DIST_SQUARED if squared else 0, C.c_void_p(index.data_ptr()),
+                                    k, flags, C.c_void_p(index.data_ptr()),
                                     C.c_void_p(dist.data_ptr()), C.byref(st)))
     return index, dist, st.as_dict()
